@@ -21,8 +21,16 @@ rank r renders rows [1080 r, 1080 (r+1)) -- bands see different content, i.e. un
 `--config 5` times BASELINE configs[4] instead: the 7680x4320 frame of the 32-primitive smooth-union scene at 256
 steps, STRONG scaling over row bands (N = 1 renders all 8 bands itself).
 
-The timed region is repeated (`--repeats`, default 5 blocks of K steps, each bracketed by barrier + synchronise);
-`value` is the median block, the spread is reported next to it.
+A plain run times exactly K steps (one block, bracketed by barrier + synchronise) after W warm-up steps and prints the
+headline: `value`, `ms_per_step` and the roofline of the timed launches.  `--full` adds everything else the benchmark
+measures, each in runs of its own: both poses with the fixed kernel choices, the 2-stream pipelined figure, config 3, the
+reference's own run shape, the first-frame (interpreter) figure, the config-4 training step and the CPU baseline; with
+`--full` the timed region is repeated (`--repeats`, default 5 blocks of K steps) and `value` is the median block, the
+spread reported next to it.
+
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (float32; a fixed, seeded
+sample of each array when all of them together exceed 64 MB).  The inputs are fixed, so two builds can be compared
+output for output.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
 """
@@ -65,7 +73,13 @@ def parse():
     ap.add_argument("--no-pipelined", action="store_true", help="skip the secondary 2-stream pipelined measurement")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0 (single-GPU box)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; value = their median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps steps; value = their median (default 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (poses, pipelined, config 3, reference shape, first frames, "
+                         "training step, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the images of the last timed step as DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--config", type=int, default=2, choices=[2, 5], help="2: headline (configs[1]); 5: configs[4], strong scaling")
     ap.add_argument("--exchange", default="p2p", choices=["p2p", "gather"], help="N>1 tile exchange: batch_isend_irecv or dist.gather")
     ap.add_argument("--skip-config3", action="store_true", help="skip the secondary 3840x2160x256 fp16 measurement")
@@ -76,7 +90,10 @@ def parse():
     ap.add_argument("--stub-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)   # tests: this rank raises before the first barrier
     ap.add_argument("--graph-leg", action="store_true", help=argparse.SUPPRESS)   # child process of the backward probe
     ap.add_argument("--interp-leg", action="store_true", help=argparse.SUPPRESS)  # child process: the frame through the LDS interpreter
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def log(msg):
@@ -598,6 +615,29 @@ class StubLoop:
         return torch.full((1, r1 - r0, self.w, 3), float(mode))
 
 
+DUMP_BUDGET_BYTES = 60_000_000       # below 64 MB with the .npy headers, whichever MB is meant
+
+
+def dump_outputs(outdir, arrays, seed=0):
+    """--dump-outputs: each array as outdir/<name>.npy, float64 kept, everything else as float32.  When all of them
+    together exceed DUMP_BUDGET_BYTES, each is replaced by the same seeded sample of its flattened elements (sorted
+    indices from numpy's default_rng(seed)), an equal share of the budget per array."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach()
+        host[name] = (a.double() if a.dtype == torch.float64 else a.float()).cpu().numpy()
+    total = sum(x.nbytes for x in host.values())
+    for name, x in host.items():
+        if total > DUMP_BUDGET_BYTES:
+            k = min(x.size, DUMP_BUDGET_BYTES // len(host) // x.itemsize)
+            idx = np.sort(np.random.default_rng(seed).choice(x.size, size=k, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(outdir, f"{name}.npy"), x)
+        log(f"dump: {name} {tuple(host[name].shape)} -> {x.size} values ({'sample' if total > DUMP_BUDGET_BYTES else 'all'})")
+
+
 def main():
     args = parse()
     if args.graph_leg:
@@ -611,6 +651,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != max(args.gpus, 1):
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    torch.manual_seed(0)          # the inputs of a run are the same from run to run (--dump-outputs compares builds)
     stub = args.stub_render
     if stub:
         dev = torch.device("cpu")
@@ -654,7 +695,7 @@ def main():
                 from ray_marching_amd.compiler import compile_scene
                 try:
                     specialize.build(compile_scene(make_scene()), precision=args.precision)
-                    if not args.skip_backward and not config5:
+                    if args.full and not args.skip_backward and not config5:
                         specialize.build(compile_scene(make_closed_test_scene()))
                 except Exception as e:      # noqa: BLE001  (no hipcc: the interpreter still renders the frame)
                     log(f"specialised libraries not built: {e}")
@@ -713,14 +754,16 @@ def main():
         # ONE preallocated buffer per frame kind; rank r's tile is received straight into rows [r*per, (r+1)*per)
         # (contiguous views: no concatenation pass).  Grey shaders are one value in three channels: they cross xGMI as
         # one channel (distributed.py)
-        gathered = []
+        gathered, gathered_whole = [], []
         for m in modes:
             whole = torch.empty(1, per * world, width, 1 if m in GREY_MODES else 3, device=dev)
             gathered.append([whole[:, r * per:(r + 1) * per] for r in range(world)])
+            gathered_whole.append(whole)
 
     kernel_ms = []
+    last_images = {}          # mode -> the image the last timed step returned (--dump-outputs)
 
-    def one_step(timed):
+    def one_step(timed, keep=False):
         if not stub:
             from ray_marching_amd import ops
         for j, mode in enumerate(modes):
@@ -730,6 +773,8 @@ def main():
             img = loop(q, t, mode, 1, march, rows=rows)
             if not stub:
                 ops.kernel_event_sink = None
+            if keep:
+                last_images[mode] = img
             if gather:
                 pay_of = lambda: tile_payload(img, mode)
                 if stub:
@@ -756,8 +801,8 @@ def main():
             dist.barrier()
         sync()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            one_step(True)
+        for i in range(args.steps):
+            one_step(True, keep=i == args.steps - 1)
         if comm is not None:
             torch.cuda.current_stream().wait_stream(comm)
         sync()
@@ -791,12 +836,20 @@ def main():
     frame_rays = rays_per_frame * (world if not config5 else 1)   # rays of the whole job's frame
     value = frame_rays * len(modes) * args.steps / elapsed / 1e6
 
+    if rank == 0 and args.dump_outputs:
+        if gathered is not None and args.backend == "nccl" and not stub:     # rank 0 of a gathering job receives the
+            # whole frame of every mode (the rehearsal backends exchange host copies and leave these buffers unwritten)
+            sync()
+            dump_outputs(args.dump_outputs, {f"frame_mode{m}": g for m, g in zip(modes, gathered_whole)})
+        else:
+            dump_outputs(args.dump_outputs, {f"image_mode{m}": img for m, img in last_images.items()})
+
     if rank == 0 and stub:
         # launcher / collective rehearsal: nothing was rendered, so there is no rate and no roofline to report
         print(json.dumps({"metric": "STUB: launcher rehearsal, no rendering (bench.py --stub-render)", "stub": True,
                           "value": None, "unit": "Mrays/s", "n_gpus": world, "requested_gpus": args.gpus,
                           "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-                          "scaling": "strong" if config5 else "weak", "data": "none (host stand-in for the renderer)",
+                          "full": args.full, "scaling": "strong" if config5 else "weak", "data": "none (host stand-in for the renderer)",
                           "config": {"workload": "stub", "backend": args.backend, "exchange": args.exchange,
                                      "work_per_rank": work_per_rank, "band": list(band),
                                      "gathered_rows": None if gathered is None else per * world}}), flush=True)
@@ -837,7 +890,7 @@ def main():
                       else "Mrays/sec at 7680x4320x256 iters, 32-primitive scene (BASELINE configs[4])",
             "value": value, "unit": "Mrays/s", "n_gpus": world, "requested_gpus": args.gpus,
             "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "full": args.full,
             "scaling": "strong" if config5 else "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "blocks": {"repeats": len(blocks), "ms_per_step": ms_blocks, "median": sorted(ms_blocks)[len(ms_blocks) // 2],
@@ -859,7 +912,8 @@ def main():
             "ray_sdf_evals_per_s": value * 1e6 * (march + 6),
             "roofline": roof,
         }
-        if world == 1 and not config5 and not args.no_pipelined:
+        # everything below takes runs of its own: --full only
+        if args.full and world == 1 and not config5 and not args.no_pipelined:
             # SURVEY 8(d) names two cameras for config 2, and they are equals here: (0,0,-3), outside the torus,
             # and the reference's own start pose (0,0,1) (main.py:46), inside the torus tube, where more rays
             # never settle.  `value` is the pose of --camera-z (default -3); both are measured the same way.
@@ -892,11 +946,11 @@ def main():
                 out["config3"] = config3_probe(dev)
             out["reference_shape"] = reference_shape_probe(dev)
             out["first_frames"] = interpreter_record()
-        if world == 1 and not args.skip_backward and not config5:      # (single-GPU legs: the other ranks would only wait for rank 0)
+        if args.full and world == 1 and not args.skip_backward and not config5:      # (single-GPU legs: the other ranks would only wait for rank 0)
             log("backward probe (config 4 shape) ...")
             out["fwd_bwd"] = backward_probe(dev)
             log(f"backward probe: {out['fwd_bwd']}")
-        if world == 1 and not args.no_cpu_baseline and not config5:
+        if args.full and world == 1 and not args.no_cpu_baseline and not config5:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -9,7 +9,7 @@ print(sys.argv[1].ljust(12), "value",round(j["value"]),"kernel_ms",round(j["roof
 '
 ARGS="--steps 30 --warmup 5 --repeats 3 --no-cpu-baseline --skip-config3"
 for i in 1 2 3; do
-  python3 bench.py $ARGS 2>/dev/null | python3 -c "$line" this_tree
+  python3 bench.py --full $ARGS 2>/dev/null | python3 -c "$line" this_tree
   (cd _ab_r2 && python3 bench.py $ARGS 2>/dev/null | python3 -c "$line" round2_tree)
-  RM_HIPCC_EXTRA=-DRM_FWD_VGPR_PARAM_LIMIT=32 RM_LIB_DIR=/tmp/rm_ab_vgpr_tile RM_SPECIALIZE=jit python3 bench.py $ARGS 2>/dev/null | python3 -c "$line" this_vgpr
+  RM_HIPCC_EXTRA=-DRM_FWD_VGPR_PARAM_LIMIT=32 RM_LIB_DIR="${TMPDIR:-/tmp}/rm_ab_vgpr_tile" RM_SPECIALIZE=jit python3 bench.py --full $ARGS 2>/dev/null | python3 -c "$line" this_vgpr
 done
