@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 13
+#define RM_ABI_VERSION 14
 
 enum {
   RM_DTYPE_F32 = 0,
@@ -91,7 +91,11 @@ enum {
                               kernels at staging time), aux0 = the child's tape slot, aux1 = n = instructions up to and including
                               the child's FOLD_LSE (whose aux1 = n).  Skips the child when its term of the logsumexp is exactly
                               +0.0f for every ray of the wave: k (d_i - d_min) > 104 (exact) */
-  RM_OP__COUNT = 19
+  RM_OP_USER = 19,         /* a user-defined leaf (ray_marching_amd/extensions.py): P: its aux1 parameters; aux0 = index of the leaf
+                              TYPE among the user types of this scene in order of first appearance, aux1 = number of parameter
+                              floats (0 allowed).  Only the per-scene specialised libraries carry handlers for it (the leaf's
+                              HIP source is compiled into them); the interpreter does not: see rm_user_leaves() */
+  RM_OP__COUNT = 20
 };
 
 /* Where one float of the parameter block lives: element `elem` of a device array of `dtype` (F32 or F16).
@@ -201,6 +205,10 @@ enum {
 
 int rm_abi_version(void);
 const char* rm_last_error(void);
+/* Number of user leaf types (RM_OP_USER handlers) this library was built with: 0 for the generic libraries and for
+ * specialised libraries of scenes without user leaves.  A program that contains RM_OP_USER must only be launched on
+ * a library that reports the scene's own count. */
+int rm_user_leaves(void);
 
 /* Workspace sizing for the backward entry points: number of floats of
  * `partials` needed for a launch over n rays. */

@@ -14,7 +14,7 @@ import os
 # ROCm-capable device is detected" (seen on the GPU box with build() followed by smoke() in one process).
 import torch  # noqa: F401,E402
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 _HERE = os.path.dirname(os.path.abspath(__file__))
 from ._build import LIB_PATH  # noqa: E402  (ray_marching_amd/lib/librm_hip.so, or under RM_LIB_DIR)
 
@@ -26,6 +26,7 @@ OP_SMOOTH_BEGIN, OP_FOLD_LSE, OP_SMOOTH_END = 12, 13, 14
 OP_ROUND, OP_ONION = 15, 16
 OP_CULL_MIN = 17
 OP_CULL_LSE = 18
+OP_USER = 19          # user-defined leaf (extensions.register_leaf): aux0 = type index in the scene, aux1 = parameter floats
 
 FLAG_EARLY_OUT, FLAG_TILE8X8, FLAG_DYNAMIC_TILES, FLAG_REGEN, FLAG_ORDER_PER_RAY = 1, 2, 4, 8, 16
 ORDER_ONE_BLOCK, ORDER_SCRATCH_INTS = 131072, 8192
@@ -66,6 +67,7 @@ _P = C.c_void_p
 _SIGNATURES = {
     "rm_abi_version": (C.c_int, []),
     "rm_last_error": (C.c_char_p, []),
+    "rm_user_leaves": (C.c_int, []),
     "rm_grad_partials_floats": (C.c_int64, [C.POINTER(RmScene), C.c_int64]),
     "rm_validate_program": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rm_sdf_forward": (C.c_int, [C.POINTER(RmScene), _P, _P, C.c_int64, C.c_int32, _P]),

@@ -38,10 +38,18 @@ _CULL_MIN_CHILD_COST = 40
 _CULL_LSE_MIN_CHILDREN = 8
 
 
+def _user_leaf(node):
+    """Registration of a user-defined leaf (extensions.register_leaf), or None."""
+    from .extensions import leaf_spec
+    return leaf_spec(node) if getattr(node, "_rm_kind", None) is None else None
+
+
 def _cost(node) -> int:
     kind = getattr(node, "_rm_kind", None)
     if kind in _LEAF_COST:
         return _LEAF_COST[kind]
+    if kind is None and _user_leaf(node) is not None:
+        return _user_leaf(node).cost
     if kind == "affine":
         return 25 + _cost(node.sdf)
     if kind in ("rounding", "onion"):
@@ -55,8 +63,8 @@ def _cost(node) -> int:
 
 def _boundable(node) -> bool:
     """Can the kernels derive a bounding sphere for this subtree (csrc/rm_device.h: subtree_bound)?
-    Everything except an SDFPlane somewhere inside; whether the bound is finite is decided on the device
-    from the live parameter values."""
+    Everything except an SDFPlane or a user-defined leaf somewhere inside; whether the bound is finite is decided
+    on the device from the live parameter values."""
     kind = getattr(node, "_rm_kind", None)
     if kind in ("sphere", "box", "line", "disk", "torus"):
         return True
@@ -78,7 +86,9 @@ class CompiledScene:
     n_grad_derived: int                 # leading derived floats that carry gradients (capsule constants)
     stack_floats: int
     n_slots: int
-    signature: tuple                    # topology key (ops + offsets), parameters excluded
+    signature: tuple                    # topology key (ops + offsets + user leaf sources), parameters excluded
+    user_leaves: tuple = ()             # (identifier, parameter floats, sha1 of the HIP source) per user leaf type, in aux0 order
+    user_sources: tuple = ()            # their HIP source texts (what specialize.code_header compiles in)
     _device_programs: dict = field(default_factory=dict)
     _table: dict = field(default_factory=dict)
     _leaf_sizes: object = None
@@ -98,6 +108,8 @@ class CompiledScene:
         scenes with many parameters always uses the generic library (accumulators in LDS).
         ``precision="fast"`` selects the opt-in fast-arithmetic builds."""
         from . import specialize
+        if self.user_leaves:
+            return self._user_leaf_lib(backward, precision)
         generic = _abi.generic_lib(precision)
         if backward and not specialize.static_backward(self):
             return generic
@@ -108,6 +120,25 @@ class CompiledScene:
         if self._lib is _abi.lib and specialize.note_interpreted_launch(self):
             self._lib = specialize.load(self) or _abi.lib      # a background build has finished
         return self._lib
+
+    def _user_leaf_lib(self, backward: bool, precision: str):
+        """Scenes with user-defined leaves (RM_OP_USER) exist only as specialised kernels: the interpreter has no
+        handler for them, so everything that would fall back to it raises instead."""
+        from . import specialize
+        names = ", ".join(name for name, _, _ in self.user_leaves)
+        if backward and not specialize.static_backward(self):
+            raise _abi.RmError(
+                f"backward of a scene with user-defined leaves ({names}) and {self.n_params + self.n_grad_derived} gradient "
+                f"accumulators: above RM_STATIC_BACKWARD_ACC={specialize._backward_limit()} the backward runs through the LDS "
+                "interpreter, which has no handler for user leaves; raise RM_STATIC_BACKWARD_ACC")
+        if precision == "exact" and self._lib is not None:
+            return self._lib
+        lib = specialize.load_user(self, precision)
+        if lib.rm_user_leaves() != len(self.user_leaves):
+            raise _abi.RmError(f"{lib._name} was built with {lib.rm_user_leaves()} user leaf types, the scene has {len(self.user_leaves)}")
+        if precision == "exact":
+            self._lib = lib
+        return lib
 
     @property
     def specialised(self) -> bool:
@@ -216,6 +247,8 @@ class _Emitter:
         # (default: also with the minimum of its children's own bounds, rm_device.h: cull_union_children)
         self.cull_union_table = os.environ.get("RM_CULL_UNION_TABLE", "1") != "0"
         self.want_table = False        # set by the parent union for the child it emits next
+        self.user_types = []           # extensions.UserLeaf of every user leaf type, in order of first appearance (= aux0)
+        self.user_floats = []          # ... and its parameter floats (= aux1)
 
     def off(self, *params):
         """Offset of the first parameter; the rest must follow contiguously."""
@@ -340,6 +373,17 @@ def _emit(node, em: _Emitter, n_params: int):
         slot = em.n_slots
         em.n_slots += 1
         em.ins(A.OP_ONION, em.off(node.radius), slot)
+    elif kind is None and _user_leaf(node) is not None:
+        from .extensions import leaf_parameters
+        spec = _user_leaf(node)
+        params = leaf_parameters(node, spec)
+        n = sum(p.numel() for p in params)
+        if spec not in em.user_types:
+            em.user_types.append(spec)
+            em.user_floats.append(n)
+        if em.user_floats[em.user_types.index(spec)] != n:
+            raise ValueError(f"{type(node).__name__}: instances of one user leaf type must have the same number of parameter floats")
+        em.ins(A.OP_USER, em.off(*params) if params else 0, em.user_types.index(spec), n)
     else:
         raise TypeError(
             f"{type(node).__name__} is not a ray_marching_amd SDF node; only the node types of "
@@ -369,9 +413,13 @@ def compile_scene(module: nn.Module) -> CompiledScene:
                                       em.max_depth, em.n_slots)
     _abi.check(rc, "rm_validate_program")
     signature = (tuple(map(tuple, program.tolist())), n_params, em.n_derived, em.max_depth, em.n_slots, em.n_grad_derived)
+    user_leaves = tuple((u.name, em.user_floats[t], u.sha1) for t, u in enumerate(em.user_types))
+    if user_leaves:
+        signature = signature + (user_leaves,)      # (scenes of built-in nodes keep the signature they always had)
     return CompiledScene(program=program, leaves=leaves, leaf_names=names, leaf_offsets=offsets,
                          n_params=n_params, n_derived=em.n_derived, n_grad_derived=em.n_grad_derived, stack_floats=em.max_depth,
-                         n_slots=em.n_slots, signature=signature)
+                         n_slots=em.n_slots, signature=signature, user_leaves=user_leaves,
+                         user_sources=tuple(u.hip for u in em.user_types))
 
 
 def structure_key(module: nn.Module):

@@ -175,6 +175,14 @@ extern "C" {
 
 int rm_abi_version(void) { return RM_ABI_VERSION; }
 
+int rm_user_leaves(void) {
+#ifdef RM_USER_LEAVES
+  return RM_USER_LEAVES;
+#else
+  return 0;
+#endif
+}
+
 const char* rm_last_error(void) { return g_err; }
 
 int64_t rm_grad_partials_floats(const RmScene* scene, int64_t n) {
@@ -687,7 +695,7 @@ int rm_sum_rows(const float* rows, int64_t n_rows, int32_t width, float* out, vo
 int rm_validate_program(const int32_t* host_program, int32_t n_instr, int32_t n_params, int32_t n_derived,
                         int32_t stack_floats, int32_t n_slots) {
   if (!host_program || n_instr <= 0) return fail(RM_E_PROGRAM, "empty program");
-  static const int psize[RM_OP__COUNT] = {0, 1, 3, 0, 7, 1, 2, 7, 7, 0, 0, 0, 0, 1, 1, 1, 1, 0, 0};
+  static const int psize[RM_OP__COUNT] = {0, 1, 3, 0, 7, 1, 2, 7, 7, 0, 0, 0, 0, 1, 1, 1, 1, 0, 0, 0};
   int depth_f = 0, depth_b = 0, max_f = 0, max_b = 0, values = 0;
   for (int i = 0; i < n_instr; ++i) {
     const int32_t* w = host_program + 4 * i;
@@ -700,6 +708,10 @@ int rm_validate_program(const int32_t* host_program, int32_t n_instr, int32_t n_
         values++;
         break;
       case RM_OP_SPHERE: case RM_OP_BOX: case RM_OP_PLANE: case RM_OP_DISK: case RM_OP_TORUS:
+        values++;
+        break;
+      case RM_OP_USER:     // aux0 = leaf type of the scene, aux1 = its parameter floats
+        if (a0 < 0 || a1 < 0 || off < 0 || off + a1 > n_params) return fail(RM_E_PROGRAM, "instr %d: user leaf params out of range", i);
         values++;
         break;
       case RM_OP_AFFINE_PUSH: depth_f += 3; depth_b += 6; break;

@@ -463,6 +463,19 @@ RM_DEV bool cull_union_children(const S& s, const PT& P, int koff, int table, in
   return (k > 0.0f) && __all(bound >= s.acc);                    // NaN anywhere: false
 }
 
+// User-defined leaves (RM_OP_USER; ray_marching_amd/extensions.py).  The code header of a specialised library is
+// included twice: here, from inside namespace rm and in front of the handlers, it contributes only its leaf section --
+// #define RM_USER_LEAVES <types>, RM_USER_MAX_PARAMS, the leaves' own device functions
+//     template <bool Fast> RM_DEV float NAME_fwd(rm::V3 p, const float* theta);
+//     template <bool Fast> RM_DEV void  NAME_vjp(rm::V3 p, const float* theta, float g, rm::V3& gp, float* gtheta);
+// and the dispatch user_leaf_fwd / user_leaf_vjp over the leaf type -- and rm_abi.hip includes it again for the program.
+// Without RM_USER_LEAVES (the generic libraries, every scene of built-in nodes) nothing below exists.
+#ifdef RM_STATIC_CODE
+#define RM_STATIC_CODE_LEAVES
+#include RM_STATIC_CODE
+#undef RM_STATIC_CODE_LEAVES
+#endif
+
 template <class S, class PT>
 RM_DEV void fwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
   switch (op) {
@@ -482,6 +495,14 @@ RM_DEV void fwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
     case RM_OP_PLANE:
       s.d = s.p.x;
       break;
+#ifdef RM_USER_LEAVES
+    case RM_OP_USER: {  // a0 = leaf type, a1 = parameter floats: constants under StaticProgram, so theta[] dissolves into P's registers
+      float theta[RM_USER_MAX_PARAMS];
+#pragma unroll
+      for (int i = 0; i < RM_USER_MAX_PARAMS; ++i) theta[i] = (i < a1) ? P[off + i] : 0.0f;
+      s.d = user_leaf_fwd<S::kFast>(a0, s.p, theta);
+    } break;
+#endif
     case RM_OP_LINE: {  // capsule; derived block holds AB and AB/|AB|^2
       V3 ab = P.v3(a0), abs_ = P.v3(a0 + 3);
       V3 ap = s.p - P.v3(off);
@@ -656,6 +677,17 @@ RM_DEV void bwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
     case RM_OP_PLANE:
       s.gp.x += s.g;
       break;
+#ifdef RM_USER_LEAVES
+    case RM_OP_USER: {
+      float theta[RM_USER_MAX_PARAMS], gtheta[RM_USER_MAX_PARAMS];
+#pragma unroll
+      for (int i = 0; i < RM_USER_MAX_PARAMS; ++i) { theta[i] = (i < a1) ? P[off + i] : 0.0f; gtheta[i] = 0.0f; }
+      user_leaf_vjp<S::kFast>(a0, s.p, theta, s.g, s.gp, gtheta);
+#pragma unroll
+      for (int i = 0; i < RM_USER_MAX_PARAMS; ++i)
+        if (i < a1) padd(s, A + off + i, gtheta[i]);
+    } break;
+#endif
     case RM_OP_LINE: {
       V3 ab = P.v3(a0), abs_ = P.v3(a0 + 3);
       V3 ap = s.p - P.v3(off);
@@ -1054,6 +1086,11 @@ RM_DEV void subtree_bound(GetIns ins, const float* P, int begin, int end, float*
         R = Ru = (hx >= 0.0f && hy >= 0.0f && hz >= 0.0f) ? sqrtf(hx * hx + hy * hy + hz * hz) : inf;
       } break;
       case RM_OP_PLANE: slope = uslope = 1.0f; R = Ru = inf; break;
+#ifdef RM_USER_LEAVES
+      // no bound is known for a user leaf.  Without this case the bound of the PREVIOUS leaf would stay in place and a union
+      // that holds a user leaf would be culled with somebody else's sphere.
+      case RM_OP_USER: cx = cy = cz = 0.0f; slope = uslope = 1.0f; R = Ru = inf; break;
+#endif
       case RM_OP_LINE: {   // capsule: sphere around the midpoint of AB
         const float* a = P + off;
         cx = 0.5f * (a[0] + a[3]); cy = 0.5f * (a[1] + a[4]); cz = 0.5f * (a[2] + a[5]);

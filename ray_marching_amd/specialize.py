@@ -21,15 +21,22 @@ Policy (env RM_SPECIALIZE):
   "prebuilt" only ever use libraries that already exist;
   "jit"      build a missing library synchronously on first use (3-14 s of hipcc);
   "off"      always interpret.
+
+Scenes with user-defined leaves (extensions.register_leaf; their HIP source is compiled into the library) have no
+interpreter to start on: "auto" and "jit" both build a missing library synchronously on first use, "prebuilt" and
+"off" raise RmError (load_user).
 """
 from __future__ import annotations
 
 import ctypes as C
 import hashlib
 import os
+import re
 import shutil
 import subprocess
+import sys
 import threading
+import time
 
 from . import _abi
 from .compiler import CompiledScene, compile_scene
@@ -84,15 +91,37 @@ def scene_hash(cs: CompiledScene, precision: str = "exact") -> str:
     return hashlib.sha1((repr(cs.signature) + sources_hash() + tag).encode()).hexdigest()[:16]
 
 
+def _leaf_section(cs: CompiledScene) -> str:
+    """User leaf sources and the dispatch over the leaf type (RM_OP_USER: aux0), for the header's first inclusion from
+    inside namespace rm (csrc/rm_device.h)."""
+    cases_f = "".join(f"    case {t}: return {name}_fwd<Fast>(p, theta);\n" for t, (name, _, _) in enumerate(cs.user_leaves))
+    cases_v = "".join(f"    case {t}: {name}_vjp<Fast>(p, theta, g, gp, gtheta); break;\n" for t, (name, _, _) in enumerate(cs.user_leaves))
+    sources = "".join(f"// user leaf {t}: {name}, {n} parameter floats, sha1 {sha}\n{src.strip()}\n"
+                      for t, ((name, n, sha), src) in enumerate(zip(cs.user_leaves, cs.user_sources)))
+    return (
+        f"#define RM_USER_LEAVES {len(cs.user_leaves)}\n"
+        f"#define RM_USER_MAX_PARAMS {max(1, max(n for _, n, _ in cs.user_leaves))}\n"
+        + sources +
+        "template <bool Fast> RM_DEV float user_leaf_fwd(int type, V3 p, const float* theta) {\n"
+        "  switch (type) {\n" + cases_f + "    default: return __builtin_nanf(\"\");\n  }\n}\n"
+        "template <bool Fast> RM_DEV void user_leaf_vjp(int type, V3 p, const float* theta, float g, V3& gp, float* gtheta) {\n"
+        "  switch (type) {\n" + cases_v + "    default: break;\n  }\n}\n")
+
+
 def code_header(cs: CompiledScene) -> str:
     rows = ",".join("{%d,%d,%d,%d}" % tuple(int(x) for x in ins) for ins in cs.program.tolist())
-    return (
-        "// generated by ray_marching_amd/specialize.py -- scene program as a compile-time constant\n"
+    program = (
         "struct RmStaticCode {\n"
         f"  static constexpr int n = {cs.n_instr}, n_params = {cs.n_params}, n_derived = {cs.n_derived},\n"
         f"                       stack_floats = {cs.stack_floats}, n_slots = {cs.n_slots}, n_grad_derived = {cs.n_grad_derived};\n"
         f"  static constexpr rm::Ins code[{cs.n_instr}] = {{{rows}}};\n"
         "};\n")
+    # included twice: by csrc/rm_device.h in front of the handlers (RM_STATIC_CODE_LEAVES: the user leaves only), then by
+    # csrc/rm_abi.hip for the program
+    head = "// generated by ray_marching_amd/specialize.py -- scene program as a compile-time constant\n"
+    if not cs.user_leaves:
+        return head + "#ifndef RM_STATIC_CODE_LEAVES\n" + program + "#endif\n"
+    return head + "#ifdef RM_STATIC_CODE_LEAVES\n" + _leaf_section(cs) + "#else\n" + program + "#endif\n"
 
 
 def lib_path(cs: CompiledScene, precision: str = "exact") -> str:
@@ -134,16 +163,37 @@ def build(cs: CompiledScene, force: bool = False, precision: str = "exact") -> s
     # several ranks may build the same scene at once: never let a concurrent hipcc read a half-written header
     text = code_header(cs)
     if not (os.path.isfile(header) and open(header).read() == text):
-        htmp = header + f".tmp{os.getpid()}"
+        htmp = header + f".tmp{os.getpid()}_{threading.get_ident()}"
         with open(htmp, "w") as f:
             f.write(text)
         os.replace(htmp, header)
-    tmp = target + f".tmp{os.getpid()}"
+    tmp = target + f".tmp{os.getpid()}_{threading.get_ident()}"      # (ranks and threads may build the same scene at once)
     cmd = [_hipcc(), *variant(precision)[1], f'-DRM_STATIC_CODE="{header}"']
     if not static_backward(cs):
         cmd.append("-DRM_NO_BACKWARD")
     cmd += [os.path.join(CSRC, "rm_abi.hip"), "-o", tmp]
-    subprocess.run(cmd, check=True, cwd=CSRC)
+    if not cs.user_leaves:
+        subprocess.run(cmd, check=True, cwd=CSRC)
+    else:
+        # user source goes through the compiler here: its diagnostics belong in the exception, and the frame kernel's
+        # occupancy in the log (a leaf slightly heavier than a torus can cost k_render_fwd its fifth wave: INTEGRATION.md)
+        t0 = time.time()
+        r = subprocess.run(cmd + ["-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True, text=True)
+        if r.returncode != 0:
+            errors = "\n".join(line for line in r.stderr.splitlines() if "remark:" not in line)
+            raise _abi.RmError(f"hipcc failed ({r.returncode}) on the specialised library of a scene with user leaves "
+                               f"({', '.join(name for name, _, _ in cs.user_leaves)}):\n{errors[-4000:]}")
+        occ, cur = [], None
+        for line in r.stderr.splitlines():
+            m = re.search(r"Function Name: (\S+)", line)
+            if m:
+                cur = m.group(1)
+            m = re.search(r"Occupancy \[waves/SIMD\]: (\d+)", line)
+            if m and cur and "k_render_fwd" in cur:
+                occ.append(int(m.group(1)))
+        print(f"ray_marching_amd: built {os.path.basename(target)} for a scene of {cs.n_instr} instructions with user leaves "
+              f"{', '.join(name for name, _, _ in cs.user_leaves)} ({precision}) in {time.time() - t0:.1f} s of hipcc; k_render_fwd "
+              f"occupancy {'/'.join(map(str, sorted(set(occ)))) or '?'} waves per SIMD", file=sys.stderr, flush=True)
     os.replace(tmp, target)
     return target
 
@@ -178,6 +228,32 @@ def load(cs: CompiledScene, precision: str = "exact"):
         if policy != "jit":
             _loaded[h] = None
             return None
+        build(cs, precision=precision)
+    lib = _abi.bind(C.CDLL(path))
+    _loaded[h] = lib
+    return lib
+
+
+def load_user(cs: CompiledScene, precision: str = "exact"):
+    """The library of a scene with user-defined leaves: never None.  "auto" and "jit" build a missing library now, on
+    first use (the interpreter cannot bridge the wait); "prebuilt" and "off" raise, naming it."""
+    policy = os.environ.get("RM_SPECIALIZE", "auto")
+    names = ", ".join(name for name, _, _ in cs.user_leaves)
+    path = lib_path(cs, precision)
+    if policy == "off":
+        raise _abi.RmError(f"RM_SPECIALIZE=off: a scene with user-defined leaves ({names}) runs only through its specialised "
+                           f"library {path}; the LDS interpreter has no handler for them")
+    h = scene_hash(cs, precision)
+    lib = _loaded.get(h)
+    if lib is not None:
+        return lib
+    if not os.path.isfile(path):
+        if policy not in ("auto", "jit"):
+            raise _abi.RmError(f"RM_SPECIALIZE={policy}: the specialised library {path} of a scene with user-defined leaves "
+                               f"({names}) has not been built (specialize.build), and the LDS interpreter has no handler for them")
+        if shutil.which(_hipcc()) is None:
+            raise _abi.RmError(f"the specialised library {path} of a scene with user-defined leaves ({names}) is missing and "
+                               "hipcc is not available to build it")
         build(cs, precision=precision)
     lib = _abi.bind(C.CDLL(path))
     _loaded[h] = lib
@@ -235,7 +311,9 @@ def ensure(module_or_cs):
 def default_scenes():
     from .scene import scene_registry as R
     from .scene.primitives import SDFSphere
+    from .contrib import make_link_scene
     return {
+        "link_scene": make_link_scene(),
         "sphere": SDFSphere(0.5),
         "make_test_scene2": R.make_test_scene2(),
         "make_test_scene": R.make_test_scene(),
