@@ -94,7 +94,10 @@ enum {
   RM_OP_USER = 19,         /* a user-defined leaf (ray_marching_amd/extensions.py): P: its aux1 parameters; aux0 = index of the leaf
                               TYPE among the user types of this scene in order of first appearance, aux1 = number of parameter
                               floats (0 allowed).  Only the per-scene specialised libraries carry handlers for it (the leaf's
-                              HIP source is compiled into them); the interpreter does not: see rm_user_leaves() */
+                              HIP source is compiled into them); the interpreter does not: see rm_user_leaves().  Its
+                              bounding sphere, where the leaf's source brings a NAME_bound, comes from that function at
+                              staging time like the built-in primitives' (cull tests may then cover it); without one it
+                              has none and no cull test is emitted over it */
   RM_OP__COUNT = 20
 };
 
@@ -217,6 +220,14 @@ int64_t rm_grad_partials_floats(const RmScene* scene, int64_t n);
 /* scene(query[...,3]) -> [...,1]          (every forward() in scene/primitives.py, transformations.py) */
 int rm_sdf_forward(const RmScene* scene, const void* points /*device [n,3]*/,
                    void* dist /*device [n]*/, int64_t n, int32_t dtype /*F32 | F16, both arrays*/, void* stream);
+
+/* Bounding sphere of the whole scene as the kernels derive it from the live parameters (the walk that fills the cull
+ * tests' bounds at staging time, run over the whole program by one block):
+ *   out[7] (device fp32) = {cx, cy, cz, R, slope, Ru, uslope}:  scene(p) >= slope |p - c| - R  for every p, 0.5 < slope <= 1;
+ *   scene(p) <= uslope |p - c| + Ru where an upper bound is known.  R / Ru = +inf: none (a plane, a user leaf without a
+ *   NAME_bound, odd parameters).  For framing a camera, for debugging a cull, and for checking the bound a user leaf signs
+ *   (extensions.check_bound); works on every library, for every scene that library can launch. */
+int rm_scene_bound(const RmScene* scene, float* out /*device [7]*/, void* stream);
 
 /* VJP of rm_sdf_forward: grad_points[n,3] (nullable) and grad_params[n_params]
  * (nullable, OVERWRITTEN with the deterministic sum over rays). */

@@ -63,11 +63,13 @@ def _cost(node) -> int:
 
 def _boundable(node) -> bool:
     """Can the kernels derive a bounding sphere for this subtree (csrc/rm_device.h: subtree_bound)?
-    Everything except an SDFPlane or a user-defined leaf somewhere inside; whether the bound is finite is decided
-    on the device from the live parameter values."""
+    Everything except an SDFPlane or a user-defined leaf registered without a NAME_bound somewhere inside; whether the
+    bound is finite is decided on the device from the live parameter values."""
     kind = getattr(node, "_rm_kind", None)
     if kind in ("sphere", "box", "line", "disk", "torus"):
         return True
+    if kind is None and _user_leaf(node) is not None:
+        return _user_leaf(node).bounded
     if kind in ("affine", "rounding", "onion"):
         return _boundable(node.sdf)
     if kind in ("union", "smooth_union"):
@@ -89,6 +91,7 @@ class CompiledScene:
     signature: tuple                    # topology key (ops + offsets + user leaf sources), parameters excluded
     user_leaves: tuple = ()             # (identifier, parameter floats, sha1 of the HIP source) per user leaf type, in aux0 order
     user_sources: tuple = ()            # their HIP source texts (what specialize.code_header compiles in)
+    user_bounded: tuple = ()            # ... and whether each source brings a NAME_bound (a bounding sphere: extensions.py)
     _device_programs: dict = field(default_factory=dict)
     _table: dict = field(default_factory=dict)
     _leaf_sizes: object = None
@@ -419,7 +422,7 @@ def compile_scene(module: nn.Module) -> CompiledScene:
     return CompiledScene(program=program, leaves=leaves, leaf_names=names, leaf_offsets=offsets,
                          n_params=n_params, n_derived=em.n_derived, n_grad_derived=em.n_grad_derived, stack_floats=em.max_depth,
                          n_slots=em.n_slots, signature=signature, user_leaves=user_leaves,
-                         user_sources=tuple(u.hip for u in em.user_types))
+                         user_sources=tuple(u.hip for u in em.user_types), user_bounded=tuple(u.bounded for u in em.user_types))
 
 
 def structure_key(module: nn.Module):

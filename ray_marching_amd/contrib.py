@@ -58,9 +58,26 @@ template <bool Fast> RM_DEV void link_vjp(rm::V3 p, const float* theta, float g,
 register_leaf(SDFLink, params=("length", "radius1", "radius2"), hip=_LINK_HIP, cost=30)
 
 
-def make_link_scene():
+class SDFBoundedLink(SDFLink):
+    """SDFLink with its bounding sphere signed (extensions: NAME_bound), so that cull tests cover it like a built-in
+    primitive: the same PyTorch forward, the same HIP op stream under an identifier of its own."""
+
+
+# the link lies inside the sphere of radius length + radius1 + radius2 around its centre (the stretched ring reaches
+# length + radius1 along y, the tube adds radius2), and it is an exact distance: slope 1 both ways
+_BLINK_HIP = _LINK_HIP.replace("link_", "blink_") + r"""
+RM_DEV void blink_bound(const float* theta, rm::LeafBound& b) {
+  if (theta[0] >= 0.0f && theta[1] >= 0.0f && theta[2] >= 0.0f) b.R = b.Ru = theta[0] + theta[1] + theta[2];
+}
+"""
+
+register_leaf(SDFBoundedLink, params=("length", "radius1", "radius2"), hip=_BLINK_HIP, cost=30)
+
+
+def make_link_scene(bounded: bool = False):
     """The room of make_test_scene2() around a sphere of 0.5 moved to x = 0.9 and a link placed by an affine node: the
-    scene whose specialised library build() compiles, so the shipped leaf renders on a box without a compiler."""
+    scene whose specialised library build() compiles, so the shipped leaf renders on a box without a compiler.
+    ``bounded``: the link is an SDFBoundedLink, and its affine node gets a cull test like the sphere's."""
     from .scene.primitives import SDFSphere
     from .scene.scene_registry import make_room
     from .scene.transformations import SDFAffineTransformation, SDFUnion
@@ -68,7 +85,7 @@ def make_link_scene():
         make_room(),
         SDFUnion(sdfs=[
             SDFAffineTransformation(SDFSphere(radius=0.5), orientation=[1.0, 0.0, 0.0, 0.0], translation=[0.9, 0.0, 0.0]),
-            SDFAffineTransformation(SDFLink(length=0.35, radius1=0.3, radius2=0.08),
+            SDFAffineTransformation((SDFBoundedLink if bounded else SDFLink)(length=0.35, radius1=0.3, radius2=0.08),
                                     orientation=[0.9014, 0.25, 0.25, 0.25], translation=[-0.6, 0.1, 0.2]),
         ]),
     ])

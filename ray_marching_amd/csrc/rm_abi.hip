@@ -209,6 +209,15 @@ int rm_sdf_forward(const RmScene* scene, const void* points, void* dist, int64_t
   return launched("k_sdf_fwd");
 }
 
+int rm_scene_bound(const RmScene* scene, float* out, void* stream) {
+  if (int e = check_scene(scene)) return e;
+  if (!out) return fail(RM_E_BADARG, "rm_scene_bound: null buffer");
+  Launch L;
+  if (int e = pick_launch(rm::k_scene_bound<G>, *scene, false, 64, &L)) return e;
+  rm::k_scene_bound<G><<<1, L.block, L.lds, (hipStream_t)stream>>>(*scene, out);
+  return launched("k_scene_bound");
+}
+
 int rm_sdf_backward(const RmScene* scene, const float* points, const float* grad_dist, float* grad_points,
                     float* grad_params, float* partials, int64_t n, void* stream) {
 #ifdef RM_NO_BACKWARD

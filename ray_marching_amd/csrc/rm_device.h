@@ -468,8 +468,21 @@ RM_DEV bool cull_union_children(const S& s, const PT& P, int koff, int table, in
 // #define RM_USER_LEAVES <types>, RM_USER_MAX_PARAMS, the leaves' own device functions
 //     template <bool Fast> RM_DEV float NAME_fwd(rm::V3 p, const float* theta);
 //     template <bool Fast> RM_DEV void  NAME_vjp(rm::V3 p, const float* theta, float g, rm::V3& gp, float* gtheta);
-// and the dispatch user_leaf_fwd / user_leaf_vjp over the leaf type -- and rm_abi.hip includes it again for the program.
-// Without RM_USER_LEAVES (the generic libraries, every scene of built-in nodes) nothing below exists.
+// and, optionally, its bounding sphere
+//     RM_DEV void NAME_bound(const float* theta, rm::LeafBound& b);
+// and the dispatch user_leaf_fwd / user_leaf_vjp / user_leaf_bound over the leaf type -- and rm_abi.hip includes it again
+// for the program.  Without RM_USER_LEAVES (the generic libraries, every scene of built-in nodes) nothing below exists.
+//
+// What a leaf signs with NAME_bound, for every p and the theta it is handed (subtree_bound calls it once per block and cull
+// site, on one lane, from the staged parameters; the margins are added there and in derive_constants, not by the leaf):
+//     NAME_fwd(p) >= slope  |p - c| - R     0.5 < slope <= 1    (1 for an exact distance whose surface lies inside (c, R))
+//     NAME_fwd(p) <= uslope |p - c| + Ru    1 <= uslope < 8     (optional: only lse_cull_mask's nearest-child estimate)
+// It arrives as "nothing known" and R = +inf (or NaN) says "no bound for these parameters".
+struct LeafBound {
+  V3 c = {0.0f, 0.0f, 0.0f};
+  float R = __builtin_inff(), slope = 1.0f;
+  float Ru = __builtin_inff(), uslope = 1.0f;
+};
 #ifdef RM_STATIC_CODE
 #define RM_STATIC_CODE_LEAVES
 #include RM_STATIC_CODE
@@ -1087,9 +1100,15 @@ RM_DEV void subtree_bound(GetIns ins, const float* P, int begin, int end, float*
       } break;
       case RM_OP_PLANE: slope = uslope = 1.0f; R = Ru = inf; break;
 #ifdef RM_USER_LEAVES
-      // no bound is known for a user leaf.  Without this case the bound of the PREVIOUS leaf would stay in place and a union
-      // that holds a user leaf would be culled with somebody else's sphere.
-      case RM_OP_USER: cx = cy = cz = 0.0f; slope = uslope = 1.0f; R = Ru = inf; break;
+      // the leaf's own NAME_bound (aux0 = leaf type), or "nothing known" when it has none.  Without this case the bound of
+      // the PREVIOUS leaf would stay in place and a union that holds a user leaf would be culled with somebody else's sphere.
+      case RM_OP_USER: {
+        LeafBound b;
+        user_leaf_bound(w.z, P + off, b);
+        cx = b.c.x; cy = b.c.y; cz = b.c.z; R = b.R; Ru = b.Ru;
+        slope = (b.slope > 1.0f) ? 1.0f : b.slope;      // (the decisions eval_near carries rest on a 1-Lipschitz test value;
+        uslope = (b.uslope < 1.0f) ? 1.0f : b.uslope;   //  a NaN stays one and fails the checks at the end of the walk)
+      } break;
 #endif
       case RM_OP_LINE: {   // capsule: sphere around the midpoint of AB
         const float* a = P + off;

@@ -77,8 +77,9 @@ struct GenericCfg {
 #ifndef RM_STATIC_REG_ACC_MAX
 #define RM_STATIC_REG_ACC_MAX 96
 #endif
-template <class Code, int kRegParamLimit = 64, bool kVgprParams = false>
+template <class Code_, int kRegParamLimit = 64, bool kVgprParams = false>
 struct StaticCfg {
+  using Code = Code_;
   static constexpr int kAcc = Code::n_params + Code::n_grad_derived;     // gradient accumulators
   // up to RM_STATIC_REG_ACC_MAX of them ride in registers, one set per ray (closed scene 1: 46); more would spill, so
   // larger scenes keep one row per wave in LDS like the interpreter (RowAccStore)
@@ -223,6 +224,28 @@ __global__ void __launch_bounds__(256) k_sdf_bwd(RmScene sc, const float* __rest
     if (live && gpts) store3(gpts, i, gp);
   }
   flush_accumulators<Cfg>(scene, n_acc, partials, rm_smem + ((sc.n_params + sc.n_derived + 3) & ~3));
+}
+
+// Bounding sphere of the whole scene (rm_scene_bound): one block stages the scene as every kernel does, then one lane
+// walks the whole program with the walk that fills the cull tests' bounds.
+template <class Cfg>
+__global__ void __launch_bounds__(64) k_scene_bound(RmScene sc, float* __restrict__ out) {
+  typename Cfg::Store store;
+  auto scene = Cfg::setup(sc, rm_smem, store);
+  __shared__ BoundFrame s_stack[kBoundDepth];
+  if (threadIdx.x == 0) {
+    float b[7];
+    if constexpr (Cfg::kStatic) {
+      using Code = typename Cfg::Code;
+      auto ins = [](int pc) { const Ins& i = Code::code[pc]; return make_int4(i.op, i.off, i.a0, i.a1); };
+      subtree_bound(ins, scene.lds, 0, Code::n, b, s_stack);
+    } else {
+      const int4* code = scene.prog.code;
+      auto ins = [code](int pc) { return code[pc]; };
+      subtree_bound(ins, scene.lds, 0, sc.n_instr, b, s_stack);
+    }
+    for (int i = 0; i < 7; ++i) out[i] = b[i];
+  }
 }
 
 // ---------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""User-defined SDF leaves: an ``nn.Module`` with its own PyTorch ``forward`` plus two HIP device functions.
+"""User-defined SDF leaves: an ``nn.Module`` with its own PyTorch ``forward`` plus two (or three) HIP device functions.
 
 The scene compiler lowers a closed vocabulary (the reference's six primitives and five combinators).  This module
 is the extension point: ``register_leaf`` teaches it one more *leaf* class, defined in the user's code, without
@@ -15,6 +15,21 @@ carry (1-ulp square roots and reciprocals inside a VJP's own forward half); INTE
 may call and the contract it signs (an exact or conservative distance, a pure function of ``p`` and ``theta``, no
 inline assembly).
 
+A third function is optional, in the same source and with the same NAME (not a template: a bound has no fast variant):
+
+    RM_DEV void NAME_bound(const float* theta, rm::LeafBound& b);
+
+the leaf's bounding sphere, which is what lets the exact cull tests cover it like a built-in primitive (without one,
+every min-union that holds the leaf loses its CULL_MIN).  ``b`` arrives as "nothing known" (``c = 0, R = +inf, slope = 1,
+Ru = +inf, uslope = 1``); by filling it in the leaf signs, for every ``p`` and the ``theta`` it is handed,
+
+    NAME_fwd(p) >= slope  * |p - c| - R     with 0.5 < slope <= 1      (needed for any culling)
+    NAME_fwd(p) <= uslope * |p - c| + Ru    with 1 <= uslope < 8       (optional; logsumexp culling's nearest-child estimate)
+
+and leaves ``R = +inf`` where it knows no bound for these parameters (a negative radius).  It runs on the device, once
+per block, from the live parameters, so it follows in-place edits and optimiser steps; the margins the kernels need
+are added by them, not by the leaf.  A wrong bound gives silently wrong pixels: run ``check_bound`` once per leaf.
+
 Scenes that contain such a leaf run only through their per-scene specialised library (specialize.py), into which
 the source is compiled; the LDS interpreter has no handler for them and ``CompiledScene.lib()`` says so instead of
 rendering a wrong picture.
@@ -28,7 +43,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn as nn
 
-__all__ = ["register_leaf", "leaf_spec", "UserLeaf"]
+__all__ = ["register_leaf", "leaf_spec", "check_bound", "UserLeaf"]
 
 
 @dataclass(frozen=True)
@@ -39,6 +54,7 @@ class UserLeaf:
     hip: str
     cost: int           # VALU estimate per evaluation (compiler._cost)
     sha1: str           # of the source: part of the scene signature, hence of the library hash
+    bounded: bool = False   # the source brings NAME_bound: cull tests may cover the leaf (read from the source, like NAME)
 
 
 _registry: dict[type, UserLeaf] = {}
@@ -58,6 +74,23 @@ def _identifier(hip: str) -> str:
     return fwd.pop()
 
 
+def _has_bound(hip: str, name: str) -> bool:
+    """Whether the source defines ``RM_DEV void NAME_bound(`` (at most one, the leaf's own NAME, not a template)."""
+    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
+    found = re.findall(r"(template\s*<[^<>]*>\s*)?RM_DEV\s+void\s+" + _DEF % "bound", text)
+    if not found:
+        return False
+    want = f"`RM_DEV void {name}_bound(const float* theta, rm::LeafBound& b)`"
+    if len(found) > 1:
+        raise ValueError(f"hip may define at most one bound function, {want} (found: {sorted(n for _, n in found)})")
+    template, got = found[0]
+    if got != name:
+        raise ValueError(f"the bound function of the leaf {name!r} must be {want}, found {got}_bound")
+    if template:
+        raise ValueError(f"{want} must not be a template: a bound has no fast variant")
+    return True
+
+
 def _device_forward(self, *args, **kwargs):
     """forward() installed by register_leaf: CUDA points go to the HIP evaluator (the leaf as a one-node scene), anything
     else to the class's own PyTorch forward."""
@@ -66,6 +99,18 @@ def _device_forward(self, *args, **kwargs):
         from .scene._base import SDFNode
         return SDFNode._evaluate(self, points)
     return type(self)._rm_torch_forward(self, *args, **kwargs)
+
+
+def _torch_forward(cls):
+    """The PyTorch forward of ``cls``: the first one in its MRO that is not the forward installed here (a subclass of a
+    registered class inherits _device_forward; its base keeps the original under _rm_torch_forward)."""
+    for c in cls.__mro__:
+        f = c.__dict__.get("forward")
+        if f is _device_forward:
+            f = c.__dict__["_rm_torch_forward"]
+        if f is not None:
+            return f
+    raise TypeError(f"register_leaf: {cls.__name__} has no forward")
 
 
 def _registered_class(cls):
@@ -91,7 +136,8 @@ def register_leaf(cls, *, params, hip: str, cost: int):
     params = tuple(params)
     if not all(isinstance(p, str) for p in params) or len(set(params)) != len(params):
         raise ValueError("register_leaf: params must be distinct attribute names")
-    spec = UserLeaf(cls, _identifier(hip), params, hip, int(cost), hashlib.sha1(hip.encode()).hexdigest())
+    name = _identifier(hip)
+    spec = UserLeaf(cls, name, params, hip, int(cost), hashlib.sha1(hip.encode()).hexdigest(), _has_bound(hip, name))
     if spec.cost < 0:
         raise ValueError("register_leaf: cost must be >= 0")
     old = _registry.get(cls)
@@ -102,7 +148,7 @@ def register_leaf(cls, *, params, hip: str, cost: int):
     for other in _registry.values():
         if other.name == spec.name:          # (two leaf types of one scene are compiled into one translation unit)
             raise ValueError(f"register_leaf: the identifier {spec.name!r} is already used by {other.cls.__name__}")
-    cls._rm_torch_forward = cls.forward
+    cls._rm_torch_forward = _torch_forward(cls)
     cls.forward = _device_forward
     _registry[cls] = spec
     return cls
@@ -120,3 +166,53 @@ def leaf_parameters(node, spec: UserLeaf):
     if missing:
         raise ValueError(f"{type(node).__name__}: registered parameter(s) {missing} are not nn.Parameter attributes of the instance")
     return [getattr(node, n) for n in spec.params]
+
+
+def check_bound(leaf, extent: float = 4.0, n: int = 1 << 16, seed: int = 0):
+    """Check the bound a leaf signs with NAME_bound against its own HIP ``NAME_fwd`` (needs a GPU; moves nothing: the
+    leaf must already be on the device).  ``n`` random points in ``[-extent, extent]^3`` and ``n`` concentrated around its
+    sphere (on it, inside it, and a few radii out) are evaluated by the kernels; the bound is read back through
+    ``rm_scene_bound`` for the leaf's current parameters.  Raises ValueError naming the worst point and by how much
+
+        fwd(p) >= slope |p - c| - R      (and, where Ru is finite,  fwd(p) <= uslope |p - c| + Ru)
+
+    fails beyond ``1e-5 * (1 + |p| + R)`` -- the fp32 rounding of the value, a tenth of the margin the kernels add.
+    Returns ``(centre, R, slope, Ru, uslope)``.  Run it once per leaf and for the parameter ranges you use: a wrong bound
+    gives silently wrong pixels."""
+    import math
+    from . import ops
+    from .scene._base import SDFNode
+    spec = leaf_spec(leaf)
+    if spec is None:
+        raise TypeError(f"check_bound: {type(leaf).__name__} is not a registered leaf")
+    if not spec.bounded:
+        raise ValueError(f"check_bound: the source of {type(leaf).__name__} defines no {spec.name}_bound")
+    params = list(leaf.parameters())
+    dev = params[0].device if params else torch.device("cuda", torch.cuda.current_device())
+    c, R, slope, Ru, uslope = ops.scene_bound(leaf, dev)
+    if not math.isfinite(R):
+        raise ValueError(f"check_bound: {spec.name}_bound gives no finite bound for these parameters (R = {R}, slope = {slope})")
+    gen = torch.Generator().manual_seed(seed)
+    box = (torch.rand(n, 3, generator=gen) * 2 - 1) * extent
+    u = torch.nn.functional.normalize(torch.randn(n, 3, generator=gen), dim=-1)
+    rho = torch.rand(n, 1, generator=gen)
+    # thirds: a shell around the sphere, the ball inside it, rays out to 8 radii (+ extent)
+    radius = torch.where(rho < 1 / 3, abs(R) * (1 + 0.1 * (rho * 6 - 1)),
+                         torch.where(rho < 2 / 3, abs(R) * (rho * 3 - 1), abs(R) + (8 * abs(R) + extent) * (rho * 3 - 2)))
+    pts = torch.cat([box, c + radius * u]).to(dev)
+    with torch.no_grad():
+        f = SDFNode._evaluate(leaf, pts).reshape(-1).double().cpu()
+    pts = pts.cpu().double()
+    dist = (pts - c.double()).norm(dim=-1)
+    tol = 1e-5 * (1 + pts.norm(dim=-1) + abs(R))
+    checks = [("lower", f - (slope * dist - R) + tol, f"{spec.name}_fwd(p) >= {slope:g} |p - c| - {R:g}")]
+    if math.isfinite(Ru):
+        checks.append(("upper", (uslope * dist + Ru) - f + tol, f"{spec.name}_fwd(p) <= {uslope:g} |p - c| + {Ru:g}"))
+    for which, margin, text in checks:
+        bad = margin.isnan() | (margin < 0)
+        if bad.any():
+            i = int(torch.where(margin.isnan(), torch.full_like(margin, -math.inf), margin).argmin())
+            raise ValueError(f"check_bound: the {which} bound of {type(leaf).__name__} fails at {int(bad.sum())} of {len(f)} points: "
+                             f"{text} with c = {c.tolist()} is off by {-float(margin[i] - tol[i]):.6g} at p = {pts[i].tolist()} "
+                             f"(value {float(f[i]):.6g})")
+    return c, R, slope, Ru, uslope

@@ -143,6 +143,27 @@ class SDFEval(torch.autograd.Function):
         return gprm[: prm.numel()], gp, None
 
 
+def scene_bound(scene, device=None):
+    """Bounding sphere of a scene (an SDF module or a CompiledScene), as the kernels derive it from the live parameters
+    (rm_scene_bound): ``(centre[3], R, slope, Ru, uslope)`` with  scene(p) >= slope |p - centre| - R  for every p and, where
+    one is known,  scene(p) <= uslope |p - centre| + Ru;  ``inf`` stands for "no bound".  For framing a camera, for
+    looking at what a cull test was given, and for checking the bound a user leaf signs (extensions.check_bound)."""
+    from .compiler import compiled_for
+    cs = scene if isinstance(scene, CompiledScene) else compiled_for(scene)
+    if device is None:
+        device = cs.leaves[0].device if cs.leaves else torch.device("cuda", torch.cuda.current_device())
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"ray_marching_amd: scene_bound needs the scene on a ROCm device, it is on {dev} "
+                           "(no CPU fallback exists by design)")
+    out = torch.empty(7, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        s, keep = cs.scene_struct(None, dev)
+        _ck(cs, cs.lib().rm_scene_bound(s, _abi.ptr(out), _abi.current_stream(dev)), "rm_scene_bound")
+    b = out.cpu()
+    return b[:3].clone(), float(b[3]), float(b[4]), float(b[5]), float(b[6])
+
+
 # --------------------------------------------------------------------------
 # marcher
 # --------------------------------------------------------------------------

@@ -93,9 +93,11 @@ def scene_hash(cs: CompiledScene, precision: str = "exact") -> str:
 
 def _leaf_section(cs: CompiledScene) -> str:
     """User leaf sources and the dispatch over the leaf type (RM_OP_USER: aux0), for the header's first inclusion from
-    inside namespace rm (csrc/rm_device.h)."""
+    inside namespace rm (csrc/rm_device.h); user_leaf_bound calls the NAME_bound of the types that bring one."""
     cases_f = "".join(f"    case {t}: return {name}_fwd<Fast>(p, theta);\n" for t, (name, _, _) in enumerate(cs.user_leaves))
     cases_v = "".join(f"    case {t}: {name}_vjp<Fast>(p, theta, g, gp, gtheta); break;\n" for t, (name, _, _) in enumerate(cs.user_leaves))
+    cases_b = "".join(f"    case {t}: {name}_bound(theta, b); break;\n"
+                      for t, ((name, _, _), bounded) in enumerate(zip(cs.user_leaves, cs.user_bounded)) if bounded)
     sources = "".join(f"// user leaf {t}: {name}, {n} parameter floats, sha1 {sha}\n{src.strip()}\n"
                       for t, ((name, n, sha), src) in enumerate(zip(cs.user_leaves, cs.user_sources)))
     return (
@@ -105,7 +107,10 @@ def _leaf_section(cs: CompiledScene) -> str:
         "template <bool Fast> RM_DEV float user_leaf_fwd(int type, V3 p, const float* theta) {\n"
         "  switch (type) {\n" + cases_f + "    default: return __builtin_nanf(\"\");\n  }\n}\n"
         "template <bool Fast> RM_DEV void user_leaf_vjp(int type, V3 p, const float* theta, float g, V3& gp, float* gtheta) {\n"
-        "  switch (type) {\n" + cases_v + "    default: break;\n  }\n}\n")
+        "  switch (type) {\n" + cases_v + "    default: break;\n  }\n}\n"
+        # (leaf types without a NAME_bound leave `b` as it arrives: nothing known)
+        "RM_DEV void user_leaf_bound(int type, const float* theta, LeafBound& b) {\n"
+        "  switch (type) {\n" + cases_b + "    default: break;\n  }\n}\n")
 
 
 def code_header(cs: CompiledScene) -> str:
@@ -314,6 +319,7 @@ def default_scenes():
     from .contrib import make_link_scene
     return {
         "link_scene": make_link_scene(),
+        "bounded_link_scene": make_link_scene(bounded=True),
         "sphere": SDFSphere(0.5),
         "make_test_scene2": R.make_test_scene2(),
         "make_test_scene": R.make_test_scene(),
