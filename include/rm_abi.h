@@ -98,8 +98,18 @@ enum {
                               bounding sphere, where the leaf's source brings a NAME_bound, comes from that function at
                               staging time like the built-in primitives' (cull tests may then cover it); without one it
                               has none and no cull test is emitted over it */
-  RM_OP__COUNT = 20
+  RM_OP_USER_FOLD = 20,    /* after a child of a user-defined combinator (extensions.register_combinator): aux0 = tape slot of the
+                              child's value (stored unconditionally, like FOLD_LSE), aux1 = tape slot of its upstream gradient,
+                              which the reverse pass of the matching USER_END fills in (= aux0 + n: a slot of its own, because
+                              the reverse pass may run twice over one tape and must leave the values as it found them) */
+  RM_OP_USER_END = 21,     /* a user-defined combinator: value = NAME_fwd(d[0..n), theta).  P: its parameters (theta); aux0 = first
+                              tape slot (n value slots, then n gradient slots), aux1 = parameter floats << 16 | combinator TYPE
+                              << 8 | n, 1 <= n <= RM_USER_COMB_MAX_CHILDREN.  A type is a (class, n) pair, numbered in order of
+                              first appearance in the scene.  Like RM_OP_USER it exists only in the per-scene specialised
+                              libraries: see rm_user_combinators().  No bound is known for it (no cull test covers it) */
+  RM_OP__COUNT = 22
 };
+#define RM_USER_COMB_MAX_CHILDREN 16
 
 /* Where one float of the parameter block lives: element `elem` of a device array of `dtype` (F32 or F16).
  * A table of n_params of these lets the kernels gather the block straight from the nn.Parameter storages in
@@ -212,6 +222,9 @@ const char* rm_last_error(void);
  * specialised libraries of scenes without user leaves.  A program that contains RM_OP_USER must only be launched on
  * a library that reports the scene's own count. */
 int rm_user_leaves(void);
+/* ... and the number of user combinator types (RM_OP_USER_END handlers; a type is a (class, child count) pair): 0 for the
+ * generic libraries.  rm_user_leaves() counts leaf types only. */
+int rm_user_combinators(void);
 
 /* Workspace sizing for the backward entry points: number of floats of
  * `partials` needed for a launch over n rays. */

@@ -44,12 +44,22 @@ def _user_leaf(node):
     return leaf_spec(node) if getattr(node, "_rm_kind", None) is None else None
 
 
+def _user_combinator(node):
+    """Registration of a user-defined combinator (extensions.register_combinator), or None."""
+    from .extensions import combinator_spec
+    return combinator_spec(node) if getattr(node, "_rm_kind", None) is None else None
+
+
 def _cost(node) -> int:
     kind = getattr(node, "_rm_kind", None)
     if kind in _LEAF_COST:
         return _LEAF_COST[kind]
     if kind is None and _user_leaf(node) is not None:
         return _user_leaf(node).cost
+    if kind is None and _user_combinator(node) is not None:
+        from .extensions import combinator_children
+        spec = _user_combinator(node)
+        return spec.cost + sum(_cost(c) + 1 for c in combinator_children(node, spec))
     if kind == "affine":
         return 25 + _cost(node.sdf)
     if kind in ("rounding", "onion"):
@@ -63,8 +73,9 @@ def _cost(node) -> int:
 
 def _boundable(node) -> bool:
     """Can the kernels derive a bounding sphere for this subtree (csrc/rm_device.h: subtree_bound)?
-    Everything except an SDFPlane or a user-defined leaf registered without a NAME_bound somewhere inside; whether the
-    bound is finite is decided on the device from the live parameter values."""
+    Everything except an SDFPlane, a user-defined leaf registered without a NAME_bound or a user-defined combinator
+    (which signs no bound) somewhere inside; whether the bound is finite is decided on the device from the live
+    parameter values."""
     kind = getattr(node, "_rm_kind", None)
     if kind in ("sphere", "box", "line", "disk", "torus"):
         return True
@@ -88,10 +99,12 @@ class CompiledScene:
     n_grad_derived: int                 # leading derived floats that carry gradients (capsule constants)
     stack_floats: int
     n_slots: int
-    signature: tuple                    # topology key (ops + offsets + user leaf sources), parameters excluded
+    signature: tuple                    # topology key (ops + offsets + user leaf / combinator sources), parameters excluded
     user_leaves: tuple = ()             # (identifier, parameter floats, sha1 of the HIP source) per user leaf type, in aux0 order
     user_sources: tuple = ()            # their HIP source texts (what specialize.code_header compiles in)
     user_bounded: tuple = ()            # ... and whether each source brings a NAME_bound (a bounding sphere: extensions.py)
+    user_combinators: tuple = ()        # (identifier, children, parameter floats, sha1) per user combinator type, in type order
+    user_combinator_sources: tuple = () # the HIP source of every combinator CLASS among them (one text per identifier)
     _device_programs: dict = field(default_factory=dict)
     _table: dict = field(default_factory=dict)
     _leaf_sizes: object = None
@@ -111,7 +124,7 @@ class CompiledScene:
         scenes with many parameters always uses the generic library (accumulators in LDS).
         ``precision="fast"`` selects the opt-in fast-arithmetic builds."""
         from . import specialize
-        if self.user_leaves:
+        if self.user_leaves or self.user_combinators:
             return self._user_leaf_lib(backward, precision)
         generic = _abi.generic_lib(precision)
         if backward and not specialize.static_backward(self):
@@ -128,17 +141,20 @@ class CompiledScene:
         """Scenes with user-defined leaves (RM_OP_USER) exist only as specialised kernels: the interpreter has no
         handler for them, so everything that would fall back to it raises instead."""
         from . import specialize
-        names = ", ".join(name for name, _, _ in self.user_leaves)
+        names, what = specialize.user_names(self)
         if backward and not specialize.static_backward(self):
             raise _abi.RmError(
-                f"backward of a scene with user-defined leaves ({names}) and {self.n_params + self.n_grad_derived} gradient "
+                f"backward of a scene with user-defined {what} ({names}) and {self.n_params + self.n_grad_derived} gradient "
                 f"accumulators: above RM_STATIC_BACKWARD_ACC={specialize._backward_limit()} the backward runs through the LDS "
-                "interpreter, which has no handler for user leaves; raise RM_STATIC_BACKWARD_ACC")
+                f"interpreter, which has no handler for user {what}; raise RM_STATIC_BACKWARD_ACC")
         if precision == "exact" and self._lib is not None:
             return self._lib
         lib = specialize.load_user(self, precision)
         if lib.rm_user_leaves() != len(self.user_leaves):
             raise _abi.RmError(f"{lib._name} was built with {lib.rm_user_leaves()} user leaf types, the scene has {len(self.user_leaves)}")
+        if lib.rm_user_combinators() != len(self.user_combinators):
+            raise _abi.RmError(f"{lib._name} was built with {lib.rm_user_combinators()} user combinator types, the scene has "
+                               f"{len(self.user_combinators)}")
         if precision == "exact":
             self._lib = lib
         return lib
@@ -252,6 +268,7 @@ class _Emitter:
         self.want_table = False        # set by the parent union for the child it emits next
         self.user_types = []           # extensions.UserLeaf of every user leaf type, in order of first appearance (= aux0)
         self.user_floats = []          # ... and its parameter floats (= aux1)
+        self.comb_types = []           # (extensions.UserCombinator, children, parameter floats) per combinator type, first appearance
 
     def off(self, *params):
         """Offset of the first parameter; the rest must follow contiguously."""
@@ -276,6 +293,7 @@ class _Emitter:
 
 
 def _emit(node, em: _Emitter, n_params: int):
+    from .extensions import leaf_parameters
     kind = getattr(node, "_rm_kind", None)
     A = _abi
     if kind == "sphere":
@@ -377,7 +395,6 @@ def _emit(node, em: _Emitter, n_params: int):
         em.n_slots += 1
         em.ins(A.OP_ONION, em.off(node.radius), slot)
     elif kind is None and _user_leaf(node) is not None:
-        from .extensions import leaf_parameters
         spec = _user_leaf(node)
         params = leaf_parameters(node, spec)
         n = sum(p.numel() for p in params)
@@ -387,6 +404,32 @@ def _emit(node, em: _Emitter, n_params: int):
         if em.user_floats[em.user_types.index(spec)] != n:
             raise ValueError(f"{type(node).__name__}: instances of one user leaf type must have the same number of parameter floats")
         em.ins(A.OP_USER, em.off(*params) if params else 0, em.user_types.index(spec), n)
+    elif kind is None and _user_combinator(node) is not None:
+        from .extensions import combinator_children
+        spec = _user_combinator(node)
+        kids = combinator_children(node, spec)
+        n = len(kids)
+        if n > A.USER_COMB_MAX_CHILDREN:
+            raise ValueError(f"{type(node).__name__}: a user combinator takes at most {A.USER_COMB_MAX_CHILDREN} children "
+                             f"(RM_USER_COMB_MAX_CHILDREN), this one has {n}; nest it")
+        params = leaf_parameters(node, spec)
+        floats = sum(p.numel() for p in params)
+        for other, _, other_floats in em.comb_types:
+            if other is spec and other_floats != floats:
+                raise ValueError(f"{type(node).__name__}: instances of one user combinator class must have the same number of parameter floats")
+        key = (spec, n, floats)
+        if key not in em.comb_types:
+            if len(em.comb_types) >= 255:
+                raise ValueError("a scene holds at most 255 user combinator types ((class, children) pairs)")
+            em.comb_types.append(key)
+        # n value slots, then n slots for the children's upstream gradients (the reverse pass leaves the values in place)
+        base = em.n_slots
+        em.n_slots += 2 * n
+        em.want_table = False          # (a bound table is asked of cullable smooth unions only)
+        for i, child in enumerate(kids):
+            _emit(child, em, n_params)
+            em.ins(A.OP_USER_FOLD, 0, base + i, base + n + i)
+        em.ins(A.OP_USER_END, em.off(*params) if params else 0, base, (floats << 16) | (em.comb_types.index(key) << 8) | n)
     else:
         raise TypeError(
             f"{type(node).__name__} is not a ray_marching_amd SDF node; only the node types of "
@@ -419,10 +462,17 @@ def compile_scene(module: nn.Module) -> CompiledScene:
     user_leaves = tuple((u.name, em.user_floats[t], u.sha1) for t, u in enumerate(em.user_types))
     if user_leaves:
         signature = signature + (user_leaves,)      # (scenes of built-in nodes keep the signature they always had)
+    user_combinators = tuple((u.name, n, floats, u.sha1) for u, n, floats in em.comb_types)
+    if user_combinators:
+        if not user_leaves:
+            signature = signature + ((),)           # (signature[-2] stays the user leaves)
+        signature = signature + (user_combinators,)
+    comb_sources = tuple({u.name: u.hip for u, _, _ in em.comb_types}.values())
     return CompiledScene(program=program, leaves=leaves, leaf_names=names, leaf_offsets=offsets,
                          n_params=n_params, n_derived=em.n_derived, n_grad_derived=em.n_grad_derived, stack_floats=em.max_depth,
                          n_slots=em.n_slots, signature=signature, user_leaves=user_leaves,
-                         user_sources=tuple(u.hip for u in em.user_types), user_bounded=tuple(u.bounded for u in em.user_types))
+                         user_sources=tuple(u.hip for u in em.user_types), user_bounded=tuple(u.bounded for u in em.user_types),
+                         user_combinators=user_combinators, user_combinator_sources=comb_sources)
 
 
 def structure_key(module: nn.Module):

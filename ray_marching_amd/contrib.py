@@ -1,12 +1,13 @@
-"""Leaves beyond the reference's six primitives, added through the public extension point (extensions.register_leaf)
-exactly as a user would add their own: a PyTorch ``forward`` (the CPU path and the oracle) and the same op stream in HIP."""
+"""Leaves and combinators beyond the reference's vocabulary, added through the public extension point
+(extensions.register_leaf / register_combinator) exactly as a user would add their own: a PyTorch ``forward`` / ``combine``
+(the CPU path and the oracle) and the same op stream in HIP."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
-from .extensions import register_leaf
+from .extensions import register_combinator, register_leaf
 
 
 class SDFLink(nn.Module):
@@ -88,4 +89,147 @@ def make_link_scene(bounded: bool = False):
             SDFAffineTransformation((SDFBoundedLink if bounded else SDFLink)(length=0.35, radius1=0.3, radius2=0.08),
                                     orientation=[0.9014, 0.25, 0.25, 0.25], translation=[-0.6, 0.1, 0.2]),
         ]),
+    ])
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# CSG combinators (extensions.register_combinator): intersection, subtraction, polynomial smooth subtraction
+# --------------------------------------------------------------------------------------------------------------------
+class _Combinator(nn.Module):
+    """Children in ``sdfs``; ``forward`` stacks their values the way the built-in unions do and hands them to ``combine``."""
+
+    def __init__(self, sdfs) -> None:
+        super().__init__()
+        self.sdfs = nn.ModuleList(sdfs)
+
+    def forward(self, query_coords: Tensor) -> Tensor:
+        return self.combine(torch.stack([sdf(query_coords) for sdf in self.sdfs], dim=-2).squeeze(-1))
+
+
+class SDFIntersection(_Combinator):
+    """max over the children: NaN propagates, the gradient goes to the first child that attains the maximum.  A lower bound
+    of the distance to the intersection (1-Lipschitz), exact on its surface."""
+
+    def combine(self, values: Tensor) -> Tensor:
+        return values.unsqueeze(-1).max(dim=-2).values
+
+
+class SDFSubtraction(_Combinator):
+    """The first child minus all the others: max(d_0, -d_1, ..., -d_{n-1}), same conventions as SDFIntersection."""
+
+    def combine(self, values: Tensor) -> Tensor:
+        return torch.cat([values[..., :1], values[..., 1:].neg()], dim=-1).unsqueeze(-1).max(dim=-2).values
+
+
+class SDFSmoothSubtraction(_Combinator):
+    """``sdfs = [a, b]``: a minus b with a polynomial fillet of width ``blend`` (> 0) instead of the crease -- the smooth maximum
+    max(x, y) + h * h * blend / 4, h = relu(blend - |x - y|) / blend, of x = d_a and y = -d_b.  No exp / log."""
+
+    def __init__(self, sdfs, blend: float) -> None:
+        super().__init__(sdfs)
+        if len(self.sdfs) != 2:
+            raise ValueError("SDFSmoothSubtraction takes exactly two children, [a, b]")
+        self.blend = nn.Parameter(torch.tensor(blend, dtype=torch.float32))
+
+    def combine(self, values: Tensor) -> Tensor:
+        x, y = values[..., 0:1], values[..., 1:2].neg()
+        h = self.blend.sub(x.sub(y).abs()).relu().div(self.blend)
+        return torch.stack([x, y], dim=-2).max(dim=-2).values.add(h.mul(h).mul(self.blend).div(4.))
+
+
+# d holds the children's values; each forward restates its combine above op for op (max(dim) is a NaN-propagating maximum:
+# t_max; the winner is the first index that attains it, or the first NaN), each VJP is autograd's, written out
+_INTERSECTION_HIP = r"""
+template <bool Fast, int N> RM_DEV float sdf_intersection_fwd(const float (&d)[N], const float* theta) {
+  float m = d[0];
+#pragma unroll
+  for (int i = 1; i < N; ++i) m = t_max(m, d[i]);
+  return m;
+}
+template <bool Fast, int N> RM_DEV void sdf_intersection_vjp(const float (&d)[N], const float* theta, float g, float (&gd)[N], float* gtheta) {
+  float m = d[0];
+#pragma unroll
+  for (int i = 1; i < N; ++i) m = t_max(m, d[i]);
+  bool open = true;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const bool win = open && (d[i] == m || (m != m && d[i] != d[i]));
+    gd[i] = win ? g : 0.0f;
+    open = open && !win;
+  }
+}
+"""
+
+_SUBTRACTION_HIP = r"""
+template <bool Fast, int N> RM_DEV float sdf_subtraction_fwd(const float (&d)[N], const float* theta) {
+  float m = d[0];
+#pragma unroll
+  for (int i = 1; i < N; ++i) m = t_max(m, -d[i]);
+  return m;
+}
+template <bool Fast, int N> RM_DEV void sdf_subtraction_vjp(const float (&d)[N], const float* theta, float g, float (&gd)[N], float* gtheta) {
+  float m = d[0];
+#pragma unroll
+  for (int i = 1; i < N; ++i) m = t_max(m, -d[i]);
+  bool open = true;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const float x = (i == 0) ? d[i] : -d[i];
+    const bool win = open && (x == m || (m != m && x != x));
+    gd[i] = win ? ((i == 0) ? g : -g) : 0.0f;
+    open = open && !win;
+  }
+}
+"""
+
+# theta = {blend}
+_SMOOTH_SUBTRACTION_HIP = r"""
+template <bool Fast, int N> RM_DEV float sdf_smooth_subtraction_fwd(const float (&d)[N], const float* theta) {
+  static_assert(N == 2, "SDFSmoothSubtraction is binary");
+  const float x = d[0], y = -d[1], b = theta[0];
+  const float h = t_max(b - fabsf(x - y), 0.0f) / b;
+  return t_max(x, y) + ((h * h) * b) / 4.0f;
+}
+template <bool Fast, int N> RM_DEV void sdf_smooth_subtraction_vjp(const float (&d)[N], const float* theta, float g, float (&gd)[N], float* gtheta) {
+  static_assert(N == 2, "SDFSmoothSubtraction is binary");
+  const float x = d[0], y = -d[1], b = theta[0];
+  const float t = x - y;
+  const float r = t_max(b - fabsf(t), 0.0f);
+  const float h = div_t<Fast>(r, b);
+  const float m = t_max(x, y);
+  const float g1 = g / 4.0f;                       // out = m + ((h h) b) / 4
+  const float gh = 2.0f * h * (g1 * b);
+  const float gr = div_t<Fast>(gh, b);             // h = r / b
+  const float ge = (r > 0.0f) ? gr : 0.0f;         // r = relu(e), e = b - |t|
+  const float gt = -ge * sgn0(t);
+  const bool first = (x == m) || (m != m && x != x);
+  const float gx = gt + (first ? g : 0.0f), gy = -gt + (first ? 0.0f : g);
+  gd[0] = gx;
+  gd[1] = -gy;
+  gtheta[0] = (g1 * (h * h) - gh * div_t<Fast>(h, b)) + ge;
+}
+"""
+
+register_combinator(SDFIntersection, hip=_INTERSECTION_HIP, cost=4)
+register_combinator(SDFSubtraction, hip=_SUBTRACTION_HIP, cost=4)
+register_combinator(SDFSmoothSubtraction, params=("blend",), hip=_SMOOTH_SUBTRACTION_HIP, cost=30)
+
+
+def make_carved_scene():
+    """The room of make_test_scene2() around two carved solids: a rotated box intersected with a sphere (rounded corners)
+    with a capsule-shaped hole drilled through it, and a sphere with a smaller sphere smoothly subtracted.  The scene whose
+    specialised library build() compiles, so the shipped combinators render on a box without a compiler."""
+    from .scene.primitives import SDFBox, SDFLine, SDFSphere
+    from .scene.scene_registry import make_room
+    from .scene.transformations import SDFAffineTransformation as A, SDFUnion
+    ident = [1.0, 0.0, 0.0, 0.0]
+    return SDFUnion([
+        make_room(),
+        SDFSubtraction([
+            SDFIntersection([A(SDFBox(halfsides=(0.5, 0.5, 0.5)), orientation=[0.9014, 0.25, 0.25, 0.25], translation=[-0.7, 0.0, 0.0]),
+                             A(SDFSphere(radius=0.66), orientation=ident, translation=[-0.7, 0.0, 0.0])]),
+            SDFLine(start=(-1.6, 0.0, 0.0), end=(0.2, 0.0, 0.0), radius=0.22),
+        ]),
+        SDFSmoothSubtraction([A(SDFSphere(radius=0.5), orientation=ident, translation=[0.9, 0.0, 0.0]),
+                              A(SDFSphere(radius=0.35), orientation=ident, translation=[0.9, 0.1, -0.45])], blend=0.15),
     ])

@@ -183,6 +183,14 @@ int rm_user_leaves(void) {
 #endif
 }
 
+int rm_user_combinators(void) {
+#ifdef RM_USER_COMBINATORS
+  return RM_USER_COMBINATORS;
+#else
+  return 0;
+#endif
+}
+
 const char* rm_last_error(void) { return g_err; }
 
 int64_t rm_grad_partials_floats(const RmScene* scene, int64_t n) {
@@ -704,7 +712,7 @@ int rm_sum_rows(const float* rows, int64_t n_rows, int32_t width, float* out, vo
 int rm_validate_program(const int32_t* host_program, int32_t n_instr, int32_t n_params, int32_t n_derived,
                         int32_t stack_floats, int32_t n_slots) {
   if (!host_program || n_instr <= 0) return fail(RM_E_PROGRAM, "empty program");
-  static const int psize[RM_OP__COUNT] = {0, 1, 3, 0, 7, 1, 2, 7, 7, 0, 0, 0, 0, 1, 1, 1, 1, 0, 0, 0};
+  static const int psize[RM_OP__COUNT] = {0, 1, 3, 0, 7, 1, 2, 7, 7, 0, 0, 0, 0, 1, 1, 1, 1, 0, 0, 0, 0, 0};
   int depth_f = 0, depth_b = 0, max_f = 0, max_b = 0, values = 0;
   for (int i = 0; i < n_instr; ++i) {
     const int32_t* w = host_program + 4 * i;
@@ -723,6 +731,35 @@ int rm_validate_program(const int32_t* host_program, int32_t n_instr, int32_t n_
         if (a0 < 0 || a1 < 0 || off < 0 || off + a1 > n_params) return fail(RM_E_PROGRAM, "instr %d: user leaf params out of range", i);
         values++;
         break;
+      case RM_OP_USER_FOLD:   // aux0 = value slot, aux1 = gradient slot; the matching USER_END checks how the two relate
+        if (a0 < 0 || a0 >= n_slots || a1 < 0 || a1 >= n_slots) return fail(RM_E_PROGRAM, "instr %d: USER_FOLD slot out of range", i);
+        values--;
+        break;
+      case RM_OP_USER_END: {  // aux0 = first slot (n values, n gradients), aux1 = parameter floats << 16 | type << 8 | n
+        const int n = a1 & 255, np = a1 >> 16;
+        if (a1 < 0 || n < 1 || n > RM_USER_COMB_MAX_CHILDREN)
+          return fail(RM_E_PROGRAM, "instr %d: user combinator of %d children (1 to %d)", i, n, RM_USER_COMB_MAX_CHILDREN);
+        if (a0 < 0 || a0 + 2 * n > n_slots) return fail(RM_E_PROGRAM, "instr %d: USER_END slots out of range", i);
+        if (off < 0 || off + np > n_params) return fail(RM_E_PROGRAM, "instr %d: user combinator params out of range", i);
+        // its n folds, walking back: child n-1 folds last; folds met while a nested combinator is open belong to that one
+        int mine = 0, nested = 0;
+        for (int j = i - 1; j >= 0 && mine < n; --j) {
+          const int32_t* v = host_program + 4 * j;
+          if (v[0] == RM_OP_USER_END) nested += v[3] & 255;
+          if (v[0] != RM_OP_USER_FOLD) continue;
+          if (nested > 0) { --nested; continue; }
+          const int child = n - 1 - mine;
+          if (v[2] != a0 + child)
+            return fail(RM_E_PROGRAM, "instr %d: USER_END of %d children: the fold of child %d (slot %d) is missing, instr %d folds slot %d",
+                        i, n, child, a0 + child, j, v[2]);
+          if (v[3] != a0 + n + child)
+            return fail(RM_E_PROGRAM, "instr %d: USER_END expects the fold of child %d at instr %d to use gradient slot %d", i, child, j,
+                        a0 + n + child);
+          ++mine;
+        }
+        if (mine != n) return fail(RM_E_PROGRAM, "instr %d: USER_END of %d children is missing %d of its folds", i, n, n - mine);
+        values++;
+      } break;
       case RM_OP_AFFINE_PUSH: depth_f += 3; depth_b += 6; break;
       case RM_OP_AFFINE_POP: depth_f -= 3; depth_b -= 6; break;
       case RM_OP_UNION_BEGIN: depth_f += 1; depth_b += 2; break;

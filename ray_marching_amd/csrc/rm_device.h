@@ -489,6 +489,42 @@ struct LeafBound {
 #undef RM_STATIC_CODE_LEAVES
 #endif
 
+// User-defined combinators (RM_OP_USER_FOLD / RM_OP_USER_END; extensions.register_combinator).  The same first inclusion of
+// the code header brings, independently of the leaves, #define RM_USER_COMBINATORS <types>, RM_USER_COMB_MAX_PARAMS, the
+// combinators' own device functions
+//     template <bool Fast, int N> RM_DEV float NAME_fwd(const float (&d)[N], const float* theta);
+//     template <bool Fast, int N> RM_DEV void  NAME_vjp(const float (&d)[N], const float* theta, float g, float (&gd)[N], float* gtheta);
+// and the dispatch user_comb_fwd / user_comb_vjp over the combinator type.  The children's values wait in n tape slots
+// (USER_FOLD stores them, like FOLD_LSE); the reverse pass meets USER_END first, runs the VJP and leaves gd[i] in the n slots
+// behind them, where the child's USER_FOLD picks it up as its upstream.  (Not in the value slots themselves: vjp_replay runs
+// the reverse pass a second time over the same tape.)  Slot range, child count and parameter count are template arguments:
+// every index into d / gd / the tape is a constant, so nothing goes to scratch memory.  StaticProgram only -- the
+// interpreter has no handler.
+#ifdef RM_USER_COMBINATORS
+template <int A0, int N, int NP, class S, class PT>
+RM_DEV void user_end_fwd(S& s, const PT& P, int off, int type) {
+  float d[N], theta[NP > 0 ? NP : 1] = {};
+#pragma unroll
+  for (int i = 0; i < N; ++i) d[i] = s.st->ld(s.tape0 + A0 + i);
+#pragma unroll
+  for (int i = 0; i < NP; ++i) theta[i] = P[off + i];
+  s.d = user_comb_fwd<S::kFast, N>(type, d, theta);
+}
+template <int A0, int N, int NP, class S, class PT>
+RM_DEV void user_end_bwd(S& s, const PT& P, int off, int type) {
+  float d[N], gd[N], theta[NP > 0 ? NP : 1] = {}, gtheta[NP > 0 ? NP : 1] = {};
+#pragma unroll
+  for (int i = 0; i < N; ++i) { d[i] = s.st->ld(s.tape0 + A0 + i); gd[i] = 0.0f; }
+#pragma unroll
+  for (int i = 0; i < NP; ++i) theta[i] = P[off + i];
+  user_comb_vjp<S::kFast, N>(type, d, theta, s.g, gd, gtheta);
+#pragma unroll
+  for (int i = 0; i < NP; ++i) padd(s, s.acc0 + off + i, gtheta[i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) s.st->st(s.tape0 + A0 + N + i, gd[i]);
+}
+#endif
+
 template <class S, class PT>
 RM_DEV void fwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
   switch (op) {
@@ -593,6 +629,11 @@ RM_DEV void fwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
       if (s.record) s.st->st(s.tape0 + a0, s.d);
       s.d = fabsf(s.d) - P[off];
       break;
+#ifdef RM_USER_COMBINATORS
+    case RM_OP_USER_FOLD:  // the child's value waits on the tape for the combinator's USER_END (StaticProgram::fwd_range)
+      s.st->st(s.tape0 + a0, s.d);
+      break;
+#endif
     default:
       break;
   }
@@ -816,6 +857,11 @@ RM_DEV void bwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
       padd(s, A + off, -s.g);
       s.g = s.g * sgn0(s.st->ld(s.tape0 + a0));
     } break;
+#ifdef RM_USER_COMBINATORS
+    case RM_OP_USER_FOLD:  // upstream of this child: gd[i], left in the gradient slot by the combinator's USER_END
+      s.g = s.st->ld(s.tape0 + a1);
+      break;
+#endif
     default:
       break;
   }
@@ -941,6 +987,11 @@ struct StaticProgram {
       } else if constexpr (i.op == RM_OP_SMOOTH_END) {
         smooth_end_static<i.a0, i.a1, smooth_culled(PC)>(s, P, i.off);
         fwd_range<PC + 1, END>(s, P);
+#ifdef RM_USER_COMBINATORS
+      } else if constexpr (i.op == RM_OP_USER_END) {
+        user_end_fwd<i.a0, (i.a1 & 255), (i.a1 >> 16)>(s, P, i.off, (i.a1 >> 8) & 255);
+        fwd_range<PC + 1, END>(s, P);
+#endif
       } else {
         fwd_op(s, P, i.op, i.off, i.a0, i.a1);
         fwd_range<PC + 1, END>(s, P);
@@ -960,6 +1011,11 @@ struct StaticProgram {
           bwd_range<PC - 1, PC - i.a1>(s, P);     // the child; PC - a1 is its CULL_MIN / CULL_LSE
         }
         bwd_range<PC - i.a1 - 1, BEGIN>(s, P);
+#ifdef RM_USER_COMBINATORS
+      } else if constexpr (i.op == RM_OP_USER_END) {
+        user_end_bwd<i.a0, (i.a1 & 255), (i.a1 >> 16)>(s, P, i.off, (i.a1 >> 8) & 255);
+        bwd_range<PC - 1, BEGIN>(s, P);
+#endif
       } else {
         if constexpr (i.op != RM_OP_CULL_MIN && i.op != RM_OP_CULL_LSE) bwd_op(s, P, i.op, i.off, i.a0, i.a1);
         bwd_range<PC - 1, BEGIN>(s, P);
@@ -1190,6 +1246,12 @@ RM_DEV void subtree_bound(GetIns ins, const float* P, int begin, int end, float*
         float k = P[off];
         R = (k > 0.0f) ? R + logf((float)st[sp].n) / k : inf;
       } break;
+#ifdef RM_USER_COMBINATORS
+      // a user combinator signs no bound (yet): nothing is known about its value, whatever its children's spheres were.
+      // Without this case the LAST child's sphere would stay in place and bound the whole combinator.
+      case RM_OP_USER_FOLD: break;
+      case RM_OP_USER_END: cx = cy = cz = 0.0f; R = Ru = inf; slope = uslope = 1.0f; break;
+#endif
       default: break;            // nested CULL_MIN / CULL_LSE: no effect on the bound
     }
   }

@@ -30,7 +30,20 @@ and leaves ``R = +inf`` where it knows no bound for these parameters (a negative
 per block, from the live parameters, so it follows in-place edits and optimiser steps; the margins the kernels need
 are added by them, not by the leaf.  A wrong bound gives silently wrong pixels: run ``check_bound`` once per leaf.
 
-Scenes that contain such a leaf run only through their per-scene specialised library (specialize.py), into which
+User-defined *combinators* are the second half of the extension point: ``register_combinator`` teaches the compiler an
+n-ary node whose value is a function of its children's values,
+
+    template <bool Fast, int N> RM_DEV float NAME_fwd(const float (&d)[N], const float* theta);
+    template <bool Fast, int N> RM_DEV void  NAME_vjp(const float (&d)[N], const float* theta, float g, float (&gd)[N], float* gtheta);
+
+``d`` holds the children's values in the module's child order, ``theta`` the node's own parameters; the VJP writes
+``gd[i] = g * df/dd_i`` and ``gtheta[j] = g * df/dtheta_j``.  ``N`` is a template parameter so that every index into ``d`` /
+``gd`` is a compile-time constant after unrolling (loops over ``N`` carry ``#pragma unroll``): an array indexed at run time
+goes to scratch memory.  The class keeps two PyTorch methods: ``combine(values [..., n]) -> [..., 1]``, the fold alone (the
+CPU path and the oracle of the HIP code), and a ``forward`` that evaluates the children and calls it.  A combinator signs no
+bound: no cull test covers a subtree that contains one (culling inside its children is untouched).
+
+Scenes that contain such a leaf or combinator run only through their per-scene specialised library (specialize.py), into which
 the source is compiled; the LDS interpreter has no handler for them and ``CompiledScene.lib()`` says so instead of
 rendering a wrong picture.
 """
@@ -43,7 +56,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn as nn
 
-__all__ = ["register_leaf", "leaf_spec", "check_bound", "UserLeaf"]
+__all__ = ["register_leaf", "leaf_spec", "check_bound", "UserLeaf", "register_combinator", "combinator_spec", "UserCombinator"]
 
 
 @dataclass(frozen=True)
@@ -57,7 +70,19 @@ class UserLeaf:
     bounded: bool = False   # the source brings NAME_bound: cull tests may cover the leaf (read from the source, like NAME)
 
 
+@dataclass(frozen=True)
+class UserCombinator:
+    cls: type
+    name: str           # NAME of NAME_fwd / NAME_vjp
+    params: tuple       # attribute names of the node's own nn.Parameters, named_parameters() order
+    hip: str
+    cost: int           # VALU estimate of the fold itself (compiler._cost adds the children's)
+    sha1: str
+    children: str       # attribute that holds the children (an nn.ModuleList or sequence of SDF modules)
+
+
 _registry: dict[type, UserLeaf] = {}
+_combinators: dict[type, UserCombinator] = {}
 
 _DEF = r"\b([A-Za-z_]\w*)_%s\s*\("
 
@@ -71,6 +96,19 @@ def _identifier(hip: str) -> str:
                          f"float g, rm::V3& gp, float* gtheta)`, with one NAME (found fwd: {sorted(fwd)}, vjp: {sorted(vjp)})")
     if re.search(r"\basm\b|__asm", text):
         raise ValueError("a user leaf must not contain inline assembly (INTEGRATION.md: leaf contract)")
+    return fwd.pop()
+
+
+def _combinator_identifier(hip: str) -> str:
+    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
+    fwd, vjp = (set(re.findall(r"RM_DEV\s+%s\s+" % ret + _DEF % kind, text)) for ret, kind in (("float", "fwd"), ("void", "vjp")))
+    if len(fwd) != 1 or fwd != vjp:
+        raise ValueError("hip must define exactly two device functions, `template <bool Fast, int N> RM_DEV float NAME_fwd(const "
+                         "float (&d)[N], const float* theta)` and `template <bool Fast, int N> RM_DEV void NAME_vjp(const float "
+                         f"(&d)[N], const float* theta, float g, float (&gd)[N], float* gtheta)`, with one NAME (found fwd: "
+                         f"{sorted(fwd)}, vjp: {sorted(vjp)})")
+    if re.search(r"\basm\b|__asm", text):
+        raise ValueError("a user combinator must not contain inline assembly (INTEGRATION.md: combinator contract)")
     return fwd.pop()
 
 
@@ -113,9 +151,10 @@ def _torch_forward(cls):
     raise TypeError(f"register_leaf: {cls.__name__} has no forward")
 
 
-def _registered_class(cls):
+def _registered_class(cls, registry=None):
+    registry = _registry if registry is None else registry
     for c in cls.__mro__:
-        if c in _registry:
+        if c in registry:
             return c
     return None
 
@@ -145,9 +184,11 @@ def register_leaf(cls, *, params, hip: str, cost: int):
         if (old.sha1, old.params, old.cost) != (spec.sha1, spec.params, spec.cost):
             raise ValueError(f"register_leaf: {cls.__name__} is already registered with different source, parameters or cost")
         return cls
-    for other in _registry.values():
-        if other.name == spec.name:          # (two leaf types of one scene are compiled into one translation unit)
+    for other in list(_registry.values()) + list(_combinators.values()):
+        if other.name == spec.name:          # (the user types of one scene are compiled into one translation unit)
             raise ValueError(f"register_leaf: the identifier {spec.name!r} is already used by {other.cls.__name__}")
+    if _registered_class(cls, _combinators) is not None:
+        raise TypeError(f"register_leaf: {cls.__name__} is already registered as a combinator")
     cls._rm_torch_forward = _torch_forward(cls)
     cls.forward = _device_forward
     _registry[cls] = spec
@@ -160,7 +201,71 @@ def leaf_spec(node):
     return None if c is None else _registry[c]
 
 
-def leaf_parameters(node, spec: UserLeaf):
+def register_combinator(cls, *, params=(), hip: str, cost: int = 4, children: str = "sdfs"):
+    """Make ``cls`` (an ``nn.Module`` subclass) compilable as an n-ary scene node whose value is ``combine`` of its
+    children's values.
+
+    params:   names of the node's OWN ``nn.Parameter`` attributes in ``named_parameters()`` order (may be empty); a module's
+              own parameters precede its children's, so they are contiguous in the scene block.
+    hip:      source of NAME_fwd / NAME_vjp (module docstring).
+    cost:     VALU instructions of the fold itself, roughly; the children's are added by the compiler.
+    children: the attribute that holds the children, an ``nn.ModuleList`` or sequence of SDF modules, n >= 1.
+
+    ``cls`` has ``combine(self, values [..., n]) -> [..., 1]`` and a ``forward(self, query_coords)`` that evaluates the
+    children and calls it.  Registration installs the same dispatch as ``register_leaf``: CUDA points go to the HIP
+    evaluator, anything else to the class's own forward (kept under ``_rm_torch_forward``).  Registering a class again with
+    the same source is a no-op; with other source, parameters, cost or children attribute it is an error.  Identifiers are
+    unique across leaves and combinators."""
+    if not (isinstance(cls, type) and issubclass(cls, nn.Module)):
+        raise TypeError(f"register_combinator: {cls!r} is not an nn.Module subclass")
+    if getattr(cls, "_rm_kind", None) is not None:
+        raise TypeError(f"register_combinator: {cls.__name__} is already a ray_marching_amd node")
+    if not callable(getattr(cls, "combine", None)):
+        raise TypeError(f"register_combinator: {cls.__name__} has no combine(values [..., n]) -> [..., 1] method")
+    if not isinstance(children, str) or not children:
+        raise ValueError("register_combinator: children must name the attribute that holds the child modules")
+    params = tuple(params)
+    if not all(isinstance(p, str) for p in params) or len(set(params)) != len(params):
+        raise ValueError("register_combinator: params must be distinct attribute names")
+    name = _combinator_identifier(hip)
+    spec = UserCombinator(cls, name, params, hip, int(cost), hashlib.sha1(hip.encode()).hexdigest(), children)
+    if spec.cost < 0:
+        raise ValueError("register_combinator: cost must be >= 0")
+    old = _combinators.get(cls)
+    if old is not None:
+        if (old.sha1, old.params, old.cost, old.children) != (spec.sha1, spec.params, spec.cost, spec.children):
+            raise ValueError(f"register_combinator: {cls.__name__} is already registered with different source, parameters, "
+                             "cost or children attribute")
+        return cls
+    if _registered_class(cls) is not None:
+        raise TypeError(f"register_combinator: {cls.__name__} is already registered as a leaf")
+    for other in list(_registry.values()) + list(_combinators.values()):
+        if other.name == spec.name:
+            raise ValueError(f"register_combinator: the identifier {spec.name!r} is already used by {other.cls.__name__}")
+    cls._rm_torch_forward = _torch_forward(cls)
+    cls.forward = _device_forward
+    _combinators[cls] = spec
+    return cls
+
+
+def combinator_spec(node):
+    """The combinator registration of this module's class (or of the registered class it derives from), or None."""
+    c = _registered_class(type(node), _combinators)
+    return None if c is None else _combinators[c]
+
+
+def combinator_children(node, spec: UserCombinator):
+    """The children of a combinator instance, in the order ``combine`` receives their values."""
+    kids = getattr(node, spec.children, None)
+    if kids is None or isinstance(kids, nn.Module) and not isinstance(kids, (nn.ModuleList, nn.Sequential)):
+        raise ValueError(f"{type(node).__name__}: the children attribute {spec.children!r} is missing or not a sequence of modules")
+    kids = list(kids)
+    if not kids or not all(isinstance(k, nn.Module) for k in kids):
+        raise ValueError(f"{type(node).__name__}: the children attribute {spec.children!r} must hold at least one SDF module")
+    return kids
+
+
+def leaf_parameters(node, spec):
     """The leaf's nn.Parameters in block order (the compiler checks that they are contiguous in the scene's block)."""
     missing = [n for n in spec.params if not isinstance(getattr(node, n, None), nn.Parameter)]
     if missing:

@@ -22,7 +22,8 @@ Policy (env RM_SPECIALIZE):
   "jit"      build a missing library synchronously on first use (3-14 s of hipcc);
   "off"      always interpret.
 
-Scenes with user-defined leaves (extensions.register_leaf; their HIP source is compiled into the library) have no
+Scenes with user-defined leaves or combinators (extensions.register_leaf / register_combinator; their HIP source is compiled
+into the library) have no
 interpreter to start on: "auto" and "jit" both build a missing library synchronously on first use, "prebuilt" and
 "off" raise RmError (load_user).
 """
@@ -113,6 +114,40 @@ def _leaf_section(cs: CompiledScene) -> str:
         "  switch (type) {\n" + cases_b + "    default: break;\n  }\n}\n")
 
 
+def _combinator_section(cs: CompiledScene) -> str:
+    """User combinator sources and the dispatch over the combinator type (RM_OP_USER_END: aux1 bits 8-15), for the same first
+    inclusion as the leaf section and independent of it.  A type is a (class, children) pair; the caller's N selects, at
+    compile time, the one instantiation of NAME_fwd / NAME_vjp a case can mean."""
+    types = cs.user_combinators
+    cases_f = "".join(f"    case {t}: if constexpr (N == {n}) return {name}_fwd<Fast, {n}>(d, theta); break;\n"
+                      for t, (name, n, _, _) in enumerate(types))
+    cases_v = "".join(f"    case {t}: if constexpr (N == {n}) {name}_vjp<Fast, {n}>(d, theta, g, gd, gtheta); break;\n"
+                      for t, (name, n, _, _) in enumerate(types))
+    listing = "".join(f"// user combinator type {t}: {name}, {n} children, {floats} parameter floats, sha1 {sha}\n"
+                      for t, (name, n, floats, sha) in enumerate(types))
+    sources = "".join(src.strip() + "\n" for src in cs.user_combinator_sources)
+    return (
+        f"#define RM_USER_COMBINATORS {len(types)}\n"
+        f"#define RM_USER_COMB_MAX_PARAMS {max(1, max(floats for _, _, floats, _ in types))}\n"
+        + listing + sources +
+        "template <bool Fast, int N> RM_DEV float user_comb_fwd(int type, const float (&d)[N], const float* theta) {\n"
+        "  switch (type) {\n" + cases_f + "    default: break;\n  }\n  return __builtin_nanf(\"\");\n}\n"
+        "template <bool Fast, int N> RM_DEV void user_comb_vjp(int type, const float (&d)[N], const float* theta, float g, "
+        "float (&gd)[N], float* gtheta) {\n"
+        "  switch (type) {\n" + cases_v + "    default: break;\n  }\n}\n")
+
+
+def user_names(cs: CompiledScene):
+    """(names, what) of the user types of a scene, for messages: leaf-only scenes read as they always did."""
+    leaves = [name for name, _, _ in cs.user_leaves]
+    combs = list(dict.fromkeys(name for name, _, _, _ in cs.user_combinators))
+    if not combs:
+        return ", ".join(leaves), "leaves"
+    if not leaves:
+        return ", ".join(combs), "combinators"
+    return "leaves: " + ", ".join(leaves) + "; combinators: " + ", ".join(combs), "leaves and combinators"
+
+
 def code_header(cs: CompiledScene) -> str:
     rows = ",".join("{%d,%d,%d,%d}" % tuple(int(x) for x in ins) for ins in cs.program.tolist())
     program = (
@@ -124,9 +159,10 @@ def code_header(cs: CompiledScene) -> str:
     # included twice: by csrc/rm_device.h in front of the handlers (RM_STATIC_CODE_LEAVES: the user leaves only), then by
     # csrc/rm_abi.hip for the program
     head = "// generated by ray_marching_amd/specialize.py -- scene program as a compile-time constant\n"
-    if not cs.user_leaves:
+    if not cs.user_leaves and not cs.user_combinators:
         return head + "#ifndef RM_STATIC_CODE_LEAVES\n" + program + "#endif\n"
-    return head + "#ifdef RM_STATIC_CODE_LEAVES\n" + _leaf_section(cs) + "#else\n" + program + "#endif\n"
+    user = (_leaf_section(cs) if cs.user_leaves else "") + (_combinator_section(cs) if cs.user_combinators else "")
+    return head + "#ifdef RM_STATIC_CODE_LEAVES\n" + user + "#else\n" + program + "#endif\n"
 
 
 def lib_path(cs: CompiledScene, precision: str = "exact") -> str:
@@ -177,7 +213,7 @@ def build(cs: CompiledScene, force: bool = False, precision: str = "exact") -> s
     if not static_backward(cs):
         cmd.append("-DRM_NO_BACKWARD")
     cmd += [os.path.join(CSRC, "rm_abi.hip"), "-o", tmp]
-    if not cs.user_leaves:
+    if not cs.user_leaves and not cs.user_combinators:
         subprocess.run(cmd, check=True, cwd=CSRC)
     else:
         # user source goes through the compiler here: its diagnostics belong in the exception, and the frame kernel's
@@ -186,8 +222,8 @@ def build(cs: CompiledScene, force: bool = False, precision: str = "exact") -> s
         r = subprocess.run(cmd + ["-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True, text=True)
         if r.returncode != 0:
             errors = "\n".join(line for line in r.stderr.splitlines() if "remark:" not in line)
-            raise _abi.RmError(f"hipcc failed ({r.returncode}) on the specialised library of a scene with user leaves "
-                               f"({', '.join(name for name, _, _ in cs.user_leaves)}):\n{errors[-4000:]}")
+            raise _abi.RmError(f"hipcc failed ({r.returncode}) on the specialised library of a scene with user {user_names(cs)[1]} "
+                               f"({user_names(cs)[0]}):\n{errors[-4000:]}")
         occ, cur = [], None
         for line in r.stderr.splitlines():
             m = re.search(r"Function Name: (\S+)", line)
@@ -196,8 +232,8 @@ def build(cs: CompiledScene, force: bool = False, precision: str = "exact") -> s
             m = re.search(r"Occupancy \[waves/SIMD\]: (\d+)", line)
             if m and cur and "k_render_fwd" in cur:
                 occ.append(int(m.group(1)))
-        print(f"ray_marching_amd: built {os.path.basename(target)} for a scene of {cs.n_instr} instructions with user leaves "
-              f"{', '.join(name for name, _, _ in cs.user_leaves)} ({precision}) in {time.time() - t0:.1f} s of hipcc; k_render_fwd "
+        print(f"ray_marching_amd: built {os.path.basename(target)} for a scene of {cs.n_instr} instructions with user {user_names(cs)[1]} "
+              f"{user_names(cs)[0]} ({precision}) in {time.time() - t0:.1f} s of hipcc; k_render_fwd "
               f"occupancy {'/'.join(map(str, sorted(set(occ)))) or '?'} waves per SIMD", file=sys.stderr, flush=True)
     os.replace(tmp, target)
     return target
@@ -243,10 +279,10 @@ def load_user(cs: CompiledScene, precision: str = "exact"):
     """The library of a scene with user-defined leaves: never None.  "auto" and "jit" build a missing library now, on
     first use (the interpreter cannot bridge the wait); "prebuilt" and "off" raise, naming it."""
     policy = os.environ.get("RM_SPECIALIZE", "auto")
-    names = ", ".join(name for name, _, _ in cs.user_leaves)
+    names, what = user_names(cs)
     path = lib_path(cs, precision)
     if policy == "off":
-        raise _abi.RmError(f"RM_SPECIALIZE=off: a scene with user-defined leaves ({names}) runs only through its specialised "
+        raise _abi.RmError(f"RM_SPECIALIZE=off: a scene with user-defined {what} ({names}) runs only through its specialised "
                            f"library {path}; the LDS interpreter has no handler for them")
     h = scene_hash(cs, precision)
     lib = _loaded.get(h)
@@ -254,10 +290,10 @@ def load_user(cs: CompiledScene, precision: str = "exact"):
         return lib
     if not os.path.isfile(path):
         if policy not in ("auto", "jit"):
-            raise _abi.RmError(f"RM_SPECIALIZE={policy}: the specialised library {path} of a scene with user-defined leaves "
+            raise _abi.RmError(f"RM_SPECIALIZE={policy}: the specialised library {path} of a scene with user-defined {what} "
                                f"({names}) has not been built (specialize.build), and the LDS interpreter has no handler for them")
         if shutil.which(_hipcc()) is None:
-            raise _abi.RmError(f"the specialised library {path} of a scene with user-defined leaves ({names}) is missing and "
+            raise _abi.RmError(f"the specialised library {path} of a scene with user-defined {what} ({names}) is missing and "
                                "hipcc is not available to build it")
         build(cs, precision=precision)
     lib = _abi.bind(C.CDLL(path))
@@ -316,7 +352,7 @@ def ensure(module_or_cs):
 def default_scenes():
     from .scene import scene_registry as R
     from .scene.primitives import SDFSphere
-    from .contrib import make_link_scene
+    from .contrib import make_carved_scene, make_link_scene
     return {
         "link_scene": make_link_scene(),
         "bounded_link_scene": make_link_scene(bounded=True),
@@ -325,6 +361,7 @@ def default_scenes():
         "make_test_scene": R.make_test_scene(),
         "make_closed_test_scene": R.make_closed_test_scene(),
         "make_many_primitive_scene32": R.make_many_primitive_scene(32),
+        "carved_scene": make_carved_scene(),
     }
 
 
