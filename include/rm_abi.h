@@ -107,7 +107,18 @@ enum {
                               << 8 | n, 1 <= n <= RM_USER_COMB_MAX_CHILDREN.  A type is a (class, n) pair, numbered in order of
                               first appearance in the scene.  Like RM_OP_USER it exists only in the per-scene specialised
                               libraries: see rm_user_combinators().  No bound is known for it (no cull test covers it) */
-  RM_OP__COUNT = 22
+  RM_OP_USER_PUSH = 22,    /* enters a user-defined domain operator (extensions.register_warp): the child that follows is evaluated at
+                              NAME_fwd(p, theta) instead of p.  P: its parameters (theta); aux0 = warp TYPE among the warp types of
+                              this scene in order of first appearance, aux1 = number of parameter floats (0 allowed).  Saves p on
+                              the frame stack like AFFINE_PUSH (3 floats forward, 6 in the reverse pass) */
+  RM_OP_USER_POP = 23,     /* leaves it: P and aux0 as on the matching PUSH; aux1 = parameter floats << 16 | (value slot + 1), low half
+                              0 when the type has no NAME_out_fwd / NAME_out_vjp.  With one, the tape slot keeps the child's value
+                              (stored by recording forward passes only, like ONION's input: the reverse pass reads it and leaves it,
+                              so a second reverse pass over the same tape, vjp_replay, finds it again) and
+                              the node's value is NAME_out_fwd(child value, p, theta), p in the node's own frame.  Like
+                              RM_OP_USER both exist only in the per-scene specialised libraries: see rm_user_warps().  No bound is
+                              known for the node (no cull test covers it; cull tests inside its child stay) */
+  RM_OP__COUNT = 24
 };
 #define RM_USER_COMB_MAX_CHILDREN 16
 
@@ -225,6 +236,9 @@ int rm_user_leaves(void);
 /* ... and the number of user combinator types (RM_OP_USER_END handlers; a type is a (class, child count) pair): 0 for the
  * generic libraries.  rm_user_leaves() counts leaf types only. */
 int rm_user_combinators(void);
+/* ... and the number of user warp types (RM_OP_USER_PUSH / RM_OP_USER_POP handlers; extensions.register_warp): 0 for the generic
+ * libraries and for every library of a scene without warps. */
+int rm_user_warps(void);
 
 /* Workspace sizing for the backward entry points: number of floats of
  * `partials` needed for a launch over n rays. */

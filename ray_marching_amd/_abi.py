@@ -30,6 +30,8 @@ OP_USER = 19          # user-defined leaf (extensions.register_leaf): aux0 = typ
 OP_USER_FOLD = 20     # after a child of a user-defined combinator (extensions.register_combinator): aux0 = value slot, aux1 = gradient slot
 OP_USER_END = 21      # the combinator itself: aux0 = first tape slot, aux1 = parameter floats << 16 | type << 8 | children
 USER_COMB_MAX_CHILDREN = 16      # RM_USER_COMB_MAX_CHILDREN
+OP_USER_PUSH = 22     # enters a user-defined domain operator (extensions.register_warp): aux0 = warp type, aux1 = parameter floats
+OP_USER_POP = 23      # leaves it: aux0 = warp type, aux1 = parameter floats << 16 | (value slot + 1; 0 = the type has no `out`)
 
 FLAG_EARLY_OUT, FLAG_TILE8X8, FLAG_DYNAMIC_TILES, FLAG_REGEN, FLAG_ORDER_PER_RAY = 1, 2, 4, 8, 16
 ORDER_ONE_BLOCK, ORDER_SCRATCH_INTS = 131072, 8192
@@ -72,6 +74,7 @@ _SIGNATURES = {
     "rm_last_error": (C.c_char_p, []),
     "rm_user_leaves": (C.c_int, []),
     "rm_user_combinators": (C.c_int, []),
+    "rm_user_warps": (C.c_int, []),
     "rm_grad_partials_floats": (C.c_int64, [C.POINTER(RmScene), C.c_int64]),
     "rm_validate_program": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rm_sdf_forward": (C.c_int, [C.POINTER(RmScene), _P, _P, C.c_int64, C.c_int32, _P]),

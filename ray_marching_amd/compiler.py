@@ -50,6 +50,12 @@ def _user_combinator(node):
     return combinator_spec(node) if getattr(node, "_rm_kind", None) is None else None
 
 
+def _user_warp(node):
+    """Registration of a user-defined domain operator (extensions.register_warp), or None."""
+    from .extensions import warp_spec
+    return warp_spec(node) if getattr(node, "_rm_kind", None) is None else None
+
+
 def _cost(node) -> int:
     kind = getattr(node, "_rm_kind", None)
     if kind in _LEAF_COST:
@@ -60,6 +66,10 @@ def _cost(node) -> int:
         from .extensions import combinator_children
         spec = _user_combinator(node)
         return spec.cost + sum(_cost(c) + 1 for c in combinator_children(node, spec))
+    if kind is None and _user_warp(node) is not None:
+        from .extensions import warp_child
+        spec = _user_warp(node)
+        return spec.cost + _cost(warp_child(node, spec))
     if kind == "affine":
         return 25 + _cost(node.sdf)
     if kind in ("rounding", "onion"):
@@ -73,8 +83,8 @@ def _cost(node) -> int:
 
 def _boundable(node) -> bool:
     """Can the kernels derive a bounding sphere for this subtree (csrc/rm_device.h: subtree_bound)?
-    Everything except an SDFPlane, a user-defined leaf registered without a NAME_bound or a user-defined combinator
-    (which signs no bound) somewhere inside; whether the bound is finite is decided on the device from the live
+    Everything except an SDFPlane, a user-defined leaf registered without a NAME_bound, a user-defined combinator or a
+    user-defined warp (which sign no bound) somewhere inside; whether the bound is finite is decided on the device from the live
     parameter values."""
     kind = getattr(node, "_rm_kind", None)
     if kind in ("sphere", "box", "line", "disk", "torus"):
@@ -99,12 +109,14 @@ class CompiledScene:
     n_grad_derived: int                 # leading derived floats that carry gradients (capsule constants)
     stack_floats: int
     n_slots: int
-    signature: tuple                    # topology key (ops + offsets + user leaf / combinator sources), parameters excluded
+    signature: tuple                    # topology key (ops + offsets + user leaf / combinator / warp sources), parameters excluded
     user_leaves: tuple = ()             # (identifier, parameter floats, sha1 of the HIP source) per user leaf type, in aux0 order
     user_sources: tuple = ()            # their HIP source texts (what specialize.code_header compiles in)
     user_bounded: tuple = ()            # ... and whether each source brings a NAME_bound (a bounding sphere: extensions.py)
     user_combinators: tuple = ()        # (identifier, children, parameter floats, sha1) per user combinator type, in type order
     user_combinator_sources: tuple = () # the HIP source of every combinator CLASS among them (one text per identifier)
+    user_warps: tuple = ()              # (identifier, parameter floats, has an `out`, sha1) per user warp type, in aux0 order
+    user_warp_sources: tuple = ()       # their HIP source texts
     _device_programs: dict = field(default_factory=dict)
     _table: dict = field(default_factory=dict)
     _leaf_sizes: object = None
@@ -124,7 +136,7 @@ class CompiledScene:
         scenes with many parameters always uses the generic library (accumulators in LDS).
         ``precision="fast"`` selects the opt-in fast-arithmetic builds."""
         from . import specialize
-        if self.user_leaves or self.user_combinators:
+        if self.user_leaves or self.user_combinators or self.user_warps:
             return self._user_leaf_lib(backward, precision)
         generic = _abi.generic_lib(precision)
         if backward and not specialize.static_backward(self):
@@ -138,7 +150,7 @@ class CompiledScene:
         return self._lib
 
     def _user_leaf_lib(self, backward: bool, precision: str):
-        """Scenes with user-defined leaves (RM_OP_USER) exist only as specialised kernels: the interpreter has no
+        """Scenes with user-defined leaves, combinators or warps (RM_OP_USER*) exist only as specialised kernels: the interpreter has no
         handler for them, so everything that would fall back to it raises instead."""
         from . import specialize
         names, what = specialize.user_names(self)
@@ -155,6 +167,8 @@ class CompiledScene:
         if lib.rm_user_combinators() != len(self.user_combinators):
             raise _abi.RmError(f"{lib._name} was built with {lib.rm_user_combinators()} user combinator types, the scene has "
                                f"{len(self.user_combinators)}")
+        if lib.rm_user_warps() != len(self.user_warps):
+            raise _abi.RmError(f"{lib._name} was built with {lib.rm_user_warps()} user warp types, the scene has {len(self.user_warps)}")
         if precision == "exact":
             self._lib = lib
         return lib
@@ -269,6 +283,8 @@ class _Emitter:
         self.user_types = []           # extensions.UserLeaf of every user leaf type, in order of first appearance (= aux0)
         self.user_floats = []          # ... and its parameter floats (= aux1)
         self.comb_types = []           # (extensions.UserCombinator, children, parameter floats) per combinator type, first appearance
+        self.warp_types = []           # extensions.UserWarp of every warp type, in order of first appearance (= aux0)
+        self.warp_floats = []          # ... and its parameter floats
 
     def off(self, *params):
         """Offset of the first parameter; the rest must follow contiguously."""
@@ -430,6 +446,36 @@ def _emit(node, em: _Emitter, n_params: int):
             _emit(child, em, n_params)
             em.ins(A.OP_USER_FOLD, 0, base + i, base + n + i)
         em.ins(A.OP_USER_END, em.off(*params) if params else 0, base, (floats << 16) | (em.comb_types.index(key) << 8) | n)
+    elif kind is None and _user_warp(node) is not None:
+        from .extensions import warp_child
+        spec = _user_warp(node)
+        kid = warp_child(node, spec)
+        params = leaf_parameters(node, spec)
+        floats = sum(p.numel() for p in params)
+        if spec not in em.warp_types:
+            if len(em.warp_types) >= 256:
+                raise ValueError("a scene holds at most 256 user warp types")
+            em.warp_types.append(spec)
+            em.warp_floats.append(floats)
+        t = em.warp_types.index(spec)
+        if em.warp_floats[t] != floats:
+            raise ValueError(f"{type(node).__name__}: instances of one user warp class must have the same number of parameter floats")
+        if floats > 32767:
+            raise ValueError(f"{type(node).__name__}: a user warp takes at most 32767 parameter floats")
+        off = em.off(*params) if params else 0
+        # a type with an `out` keeps its child's value in a tape slot of its own (the reverse pass reads it)
+        slot1 = 0
+        if spec.has_out:
+            slot1 = em.n_slots + 1
+            em.n_slots += 1
+            if slot1 > 65535:
+                raise ValueError("too many tape slots for a user warp with an `out` (65535)")
+        em.want_table = False          # (a bound table is asked of cullable smooth unions only)
+        em.ins(A.OP_USER_PUSH, off, t, floats)
+        em.push(_STACK_AFFINE)
+        _emit(kid, em, n_params)
+        em.pop(_STACK_AFFINE)
+        em.ins(A.OP_USER_POP, off, t, (floats << 16) | slot1)
     else:
         raise TypeError(
             f"{type(node).__name__} is not a ray_marching_amd SDF node; only the node types of "
@@ -468,11 +514,15 @@ def compile_scene(module: nn.Module) -> CompiledScene:
             signature = signature + ((),)           # (signature[-2] stays the user leaves)
         signature = signature + (user_combinators,)
     comb_sources = tuple({u.name: u.hip for u, _, _ in em.comb_types}.values())
+    user_warps = tuple((u.name, em.warp_floats[t], u.has_out, u.sha1) for t, u in enumerate(em.warp_types))
+    if user_warps:
+        signature = signature + ((),) * (8 - len(signature)) + (user_warps,)      # (signature[-3], [-2] stay leaves, combinators)
     return CompiledScene(program=program, leaves=leaves, leaf_names=names, leaf_offsets=offsets,
                          n_params=n_params, n_derived=em.n_derived, n_grad_derived=em.n_grad_derived, stack_floats=em.max_depth,
                          n_slots=em.n_slots, signature=signature, user_leaves=user_leaves,
                          user_sources=tuple(u.hip for u in em.user_types), user_bounded=tuple(u.bounded for u in em.user_types),
-                         user_combinators=user_combinators, user_combinator_sources=comb_sources)
+                         user_combinators=user_combinators, user_combinator_sources=comb_sources,
+                         user_warps=user_warps, user_warp_sources=tuple(u.hip for u in em.warp_types))
 
 
 def structure_key(module: nn.Module):

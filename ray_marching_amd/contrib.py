@@ -1,13 +1,13 @@
-"""Leaves and combinators beyond the reference's vocabulary, added through the public extension point
-(extensions.register_leaf / register_combinator) exactly as a user would add their own: a PyTorch ``forward`` / ``combine``
-(the CPU path and the oracle) and the same op stream in HIP."""
+"""Leaves, combinators and domain operators beyond the reference's vocabulary, added through the public extension point
+(extensions.register_leaf / register_combinator / register_warp) exactly as a user would add their own: a PyTorch ``forward`` /
+``combine`` / ``warp`` (the CPU path and the oracle) and the same op stream in HIP."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
-from .extensions import register_combinator, register_leaf
+from .extensions import register_combinator, register_leaf, register_warp
 
 
 class SDFLink(nn.Module):
@@ -232,4 +232,166 @@ def make_carved_scene():
         ]),
         SDFSmoothSubtraction([A(SDFSphere(radius=0.5), orientation=ident, translation=[0.9, 0.0, 0.0]),
                               A(SDFSphere(radius=0.35), orientation=ident, translation=[0.9, 0.1, -0.45])], blend=0.15),
+    ])
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# Domain operators (extensions.register_warp): uniform scale, mirror symmetry, repetition, elongation
+# --------------------------------------------------------------------------------------------------------------------
+class _Warp(nn.Module):
+    """One child in ``sdf``; ``forward`` evaluates it at ``warp(p)`` and hands its value to ``out`` where the class has one."""
+
+    def __init__(self, sdf) -> None:
+        super().__init__()
+        self.sdf = sdf
+
+    def forward(self, query_coords: Tensor) -> Tensor:
+        values = self.sdf(self.warp(query_coords))
+        return self.out(values, query_coords) if hasattr(self, "out") else values
+
+
+class SDFScale(_Warp):
+    """The child scaled uniformly by ``scale`` (> 0) about the origin: ``scale * sdf(p / scale)``, an exact distance where the
+    child's is."""
+
+    def __init__(self, sdf, scale: float) -> None:
+        super().__init__(sdf)
+        self.scale = nn.Parameter(torch.tensor(scale, dtype=torch.float32))
+
+    def warp(self, points: Tensor) -> Tensor:
+        return points.div(self.scale)
+
+    def out(self, values: Tensor, points: Tensor) -> Tensor:
+        return values.mul(self.scale)
+
+
+class SDFMirror(_Warp):
+    """The half x >= ``origin`` of the child, mirrored in the plane x = ``origin`` (wrap it in an affine node for any other
+    plane): ``sdf(|p.x - origin|, p.y, p.z)``.  A lower bound of the distance where the child crosses the plane."""
+
+    def __init__(self, sdf, origin: float = 0.0) -> None:
+        super().__init__(sdf)
+        self.origin = nn.Parameter(torch.tensor(origin, dtype=torch.float32))
+
+    def warp(self, points: Tensor) -> Tensor:
+        return torch.cat([points[..., :1].sub(self.origin).abs(), points[..., 1:]], dim=-1)
+
+
+class SDFRepeat(_Warp):
+    """The child repeated without end on the grid of cell size ``period`` (> 0 on every axis): ``sdf(p - period * round(p /
+    period))``.  A distance as long as the child stays inside its cell, |x_i| <= period_i / 2, and is symmetric enough that the
+    neighbouring cell's copy is never nearer.  ``round`` is half-to-even and has a zero gradient, as in autograd."""
+
+    def __init__(self, sdf, period) -> None:
+        super().__init__(sdf)
+        self.period = nn.Parameter(torch.tensor(period, dtype=torch.float32))
+
+    def warp(self, points: Tensor) -> Tensor:
+        return points.sub(self.period.mul(points.div(self.period).round()))
+
+
+class SDFElongate(_Warp):
+    """The child pulled apart by ``2 * halfsides`` (> 0) along the axes: ``sdf(p - clamp(p, -halfsides, halfsides))``.  The map is
+    1-Lipschitz, so the field stays a conservative distance."""
+
+    def __init__(self, sdf, halfsides) -> None:
+        super().__init__(sdf)
+        self.halfsides = nn.Parameter(torch.tensor(halfsides, dtype=torch.float32))
+
+    def warp(self, points: Tensor) -> Tensor:
+        return points.sub(points.clamp(self.halfsides.neg(), self.halfsides))
+
+
+# theta = {scale}.  The forwards are ATen's ops, one rounding each, with a plain `/`: values never go through Fast.  The VJPs
+# are the gradients autograd computes (grad / other for the point; for the divisor the sum over the three coordinates, in
+# index order, of -grad * self / other^2), not its op stream: ATen groups the divisor's term as -grad * ((self / other) /
+# other), which differs in the last bits, far inside the 1e-4 a gradient is held to; `div_t<Fast>` as in the built-in VJPs.
+_SCALE_HIP = r"""
+template <bool Fast> RM_DEV rm::V3 sdf_scale_fwd(rm::V3 p, const float* theta) {
+  return mk3(p.x / theta[0], p.y / theta[0], p.z / theta[0]);
+}
+template <bool Fast> RM_DEV void sdf_scale_vjp(rm::V3 p, const float* theta, rm::V3 gq, rm::V3& gp, float* gtheta) {
+  const float s = theta[0], s2 = s * s;
+  gp.x += div_t<Fast>(gq.x, s); gp.y += div_t<Fast>(gq.y, s); gp.z += div_t<Fast>(gq.z, s);
+  gtheta[0] = (div_t<Fast>(-gq.x * p.x, s2) + div_t<Fast>(-gq.y * p.y, s2)) + div_t<Fast>(-gq.z * p.z, s2);
+}
+template <bool Fast> RM_DEV float sdf_scale_out_fwd(float d, rm::V3 p, const float* theta) { return d * theta[0]; }
+template <bool Fast> RM_DEV void sdf_scale_out_vjp(float d, rm::V3 p, const float* theta, float g, float& gd, rm::V3& gp, float* gtheta) {
+  gd = g * theta[0];
+  gtheta[0] = g * d;
+}
+"""
+
+# theta = {origin}; abs backward is grad * sign(x), 0 at 0: sgn0, as in the box handler
+_MIRROR_HIP = r"""
+template <bool Fast> RM_DEV rm::V3 sdf_mirror_fwd(rm::V3 p, const float* theta) {
+  return mk3(fabsf(p.x - theta[0]), p.y, p.z);
+}
+template <bool Fast> RM_DEV void sdf_mirror_vjp(rm::V3 p, const float* theta, rm::V3 gq, rm::V3& gp, float* gtheta) {
+  const float gx = gq.x * sgn0(p.x - theta[0]);
+  gp.x += gx; gp.y += gq.y; gp.z += gq.z;
+  gtheta[0] = -gx;
+}
+"""
+
+# theta = {period[3]}; torch.round is half-to-even: rintf.  round has a zero gradient, so dq/dp = 1 and dq/dperiod_i = -round(.)
+_REPEAT_HIP = r"""
+template <bool Fast> RM_DEV rm::V3 sdf_repeat_fwd(rm::V3 p, const float* theta) {
+  return mk3(p.x - theta[0] * rintf(p.x / theta[0]), p.y - theta[1] * rintf(p.y / theta[1]), p.z - theta[2] * rintf(p.z / theta[2]));
+}
+template <bool Fast> RM_DEV void sdf_repeat_vjp(rm::V3 p, const float* theta, rm::V3 gq, rm::V3& gp, float* gtheta) {
+  gp.x += gq.x; gp.y += gq.y; gp.z += gq.z;
+  gtheta[0] = -gq.x * rintf(p.x / theta[0]);
+  gtheta[1] = -gq.y * rintf(p.y / theta[1]);
+  gtheta[2] = -gq.z * rintf(p.z / theta[2]);
+}
+"""
+
+# theta = {halfsides[3]}; clamp(x, lo, hi) = min(max(x, lo), hi) with NaN passing: t_clamp.  clamp passes its gradient to x on
+# the closed interval [lo, hi] (as the capsule handler notes), to lo where x < lo and to hi where x > hi; lo = -h.
+_ELONGATE_HIP = r"""
+template <bool Fast> RM_DEV rm::V3 sdf_elongate_fwd(rm::V3 p, const float* theta) {
+  return mk3(p.x - t_clamp(p.x, -theta[0], theta[0]), p.y - t_clamp(p.y, -theta[1], theta[1]), p.z - t_clamp(p.z, -theta[2], theta[2]));
+}
+template <bool Fast> RM_DEV void sdf_elongate_vjp(rm::V3 p, const float* theta, rm::V3 gq, rm::V3& gp, float* gtheta) {
+  const float x[3] = {p.x, p.y, p.z}, g[3] = {gq.x, gq.y, gq.z};
+  float out[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const float h = theta[i];
+    const bool inside = (x[i] >= -h) && (x[i] <= h);
+    out[i] = inside ? 0.0f : g[i];                       // q = x - clamp(x): 1 - [lo <= x <= hi]
+    const bool ordered = -h < h;                          // (autograd's rule for lo >= hi: everything goes to hi)
+    const float glo = (ordered && x[i] < -h) ? -g[i] : 0.0f;
+    const float ghi = (!ordered || x[i] > h) ? -g[i] : 0.0f;
+    gtheta[i] = ghi - glo;
+  }
+  gp.x += out[0]; gp.y += out[1]; gp.z += out[2];
+}
+"""
+
+register_warp(SDFScale, params=("scale",), hip=_SCALE_HIP, cost=36)
+register_warp(SDFMirror, params=("origin",), hip=_MIRROR_HIP, cost=3)
+register_warp(SDFRepeat, params=("period",), hip=_REPEAT_HIP, cost=45)
+register_warp(SDFElongate, params=("halfsides",), hip=_ELONGATE_HIP, cost=12)
+
+
+def make_warped_scene():
+    """The room of make_test_scene2() around an arrangement that uses all four operators: a scaled torus and an elongated
+    sphere, each placed by an affine node, in a union that is mirrored in the plane x = 0 and lifted by another affine node;
+    and a grid of small spheres (SDFRepeat) cut to a slab by an SDFIntersection with a box.  The scene whose specialised
+    library build() compiles, so the shipped operators render on a box without a compiler."""
+    from .scene.primitives import SDFBox, SDFSphere, SDFTorus
+    from .scene.scene_registry import make_room
+    from .scene.transformations import SDFAffineTransformation as A, SDFUnion
+    ident = [1.0, 0.0, 0.0, 0.0]
+    pair = SDFUnion([
+        A(SDFScale(SDFTorus(radius1=0.5, radius2=0.12), scale=0.7), orientation=[0.9014, 0.25, 0.25, 0.25], translation=[0.9, 0.4, 0.2]),
+        A(SDFElongate(SDFSphere(radius=0.2), halfsides=(0.05, 0.3, 0.1)), orientation=ident, translation=[0.5, -0.5, -0.3]),
+    ])
+    return SDFUnion([
+        make_room(),
+        A(SDFMirror(pair, origin=0.0), orientation=ident, translation=[0.0, 0.2, 0.0]),
+        SDFIntersection([SDFRepeat(SDFSphere(radius=0.12), period=(0.5, 0.5, 0.5)),
+                         A(SDFBox(halfsides=(1.2, 0.2, 1.2)), orientation=ident, translation=[0.0, -1.4, 0.0])]),
     ])

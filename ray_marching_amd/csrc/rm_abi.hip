@@ -191,6 +191,14 @@ int rm_user_combinators(void) {
 #endif
 }
 
+int rm_user_warps(void) {
+#ifdef RM_USER_WARPS
+  return RM_USER_WARPS;
+#else
+  return 0;
+#endif
+}
+
 const char* rm_last_error(void) { return g_err; }
 
 int64_t rm_grad_partials_floats(const RmScene* scene, int64_t n) {
@@ -712,7 +720,7 @@ int rm_sum_rows(const float* rows, int64_t n_rows, int32_t width, float* out, vo
 int rm_validate_program(const int32_t* host_program, int32_t n_instr, int32_t n_params, int32_t n_derived,
                         int32_t stack_floats, int32_t n_slots) {
   if (!host_program || n_instr <= 0) return fail(RM_E_PROGRAM, "empty program");
-  static const int psize[RM_OP__COUNT] = {0, 1, 3, 0, 7, 1, 2, 7, 7, 0, 0, 0, 0, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+  static const int psize[RM_OP__COUNT] = {0, 1, 3, 0, 7, 1, 2, 7, 7, 0, 0, 0, 0, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
   int depth_f = 0, depth_b = 0, max_f = 0, max_b = 0, values = 0;
   for (int i = 0; i < n_instr; ++i) {
     const int32_t* w = host_program + 4 * i;
@@ -759,6 +767,29 @@ int rm_validate_program(const int32_t* host_program, int32_t n_instr, int32_t n_
         }
         if (mine != n) return fail(RM_E_PROGRAM, "instr %d: USER_END of %d children is missing %d of its folds", i, n, n - mine);
         values++;
+      } break;
+      case RM_OP_USER_PUSH:   // aux0 = warp type, aux1 = parameter floats; a frame like the affine one
+        if (a0 < 0 || a0 > 255 || a1 < 0 || a1 > 32767 || off < 0 || off + a1 > n_params)
+          return fail(RM_E_PROGRAM, "instr %d: user warp params out of range", i);
+        depth_f += 3; depth_b += 6;
+        break;
+      case RM_OP_USER_POP: {  // aux0 = warp type, aux1 = parameter floats << 16 | (value slot + 1, 0 = none)
+        const int np = a1 >> 16, slot = (a1 & 65535) - 1;
+        if (a0 < 0 || a1 < 0 || off < 0 || off + np > n_params) return fail(RM_E_PROGRAM, "instr %d: user warp params out of range", i);
+        if (slot >= n_slots) return fail(RM_E_PROGRAM, "instr %d: USER_POP value slot %d out of range", i, slot);
+        // its PUSH, walking back over the frames (affine ones too) that opened and closed in between
+        int open = 0, j = i - 1;
+        for (; j >= 0; --j) {
+          const int o = host_program[4 * j];
+          if (o == RM_OP_USER_POP || o == RM_OP_AFFINE_POP) ++open;
+          if ((o == RM_OP_USER_PUSH || o == RM_OP_AFFINE_PUSH) && open-- == 0) break;
+        }
+        if (j < 0 || host_program[4 * j] != RM_OP_USER_PUSH) return fail(RM_E_PROGRAM, "instr %d: USER_POP without a USER_PUSH", i);
+        const int32_t* v = host_program + 4 * j;
+        if (v[1] != off || v[2] != a0 || v[3] != np)
+          return fail(RM_E_PROGRAM, "instr %d: USER_POP {offset %d, type %d, %d floats} does not match its USER_PUSH at instr %d {%d, %d, %d}",
+                      i, off, a0, np, j, v[1], v[2], v[3]);
+        depth_f -= 3; depth_b -= 6;
       } break;
       case RM_OP_AFFINE_PUSH: depth_f += 3; depth_b += 6; break;
       case RM_OP_AFFINE_POP: depth_f -= 3; depth_b -= 6; break;

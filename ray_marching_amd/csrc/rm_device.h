@@ -525,6 +525,20 @@ RM_DEV void user_end_bwd(S& s, const PT& P, int off, int type) {
 }
 #endif
 
+// User-defined domain operators (RM_OP_USER_PUSH / RM_OP_USER_POP; extensions.register_warp): unary nodes that move the query
+// point before their child is evaluated and, optionally, edit the value it returns.  The first inclusion of the code header
+// brings, independently of leaves and combinators, #define RM_USER_WARPS <types>, RM_USER_WARP_MAX_PARAMS, the operators' own
+// device functions (p is the point in the node's own frame in all four)
+//     template <bool Fast> RM_DEV rm::V3 NAME_fwd(rm::V3 p, const float* theta);                                   // the child's point
+//     template <bool Fast> RM_DEV void   NAME_vjp(rm::V3 p, const float* theta, rm::V3 gq, rm::V3& gp, float* gtheta);
+//     template <bool Fast> RM_DEV float  NAME_out_fwd(float d, rm::V3 p, const float* theta);                      // optional pair
+//     template <bool Fast> RM_DEV void   NAME_out_vjp(float d, rm::V3 p, const float* theta, float g, float& gd, rm::V3& gp, float* gtheta);
+// and the dispatch user_warp_fwd / _vjp / _out_fwd / _out_vjp over the warp type.  The protocol is the affine pair's: PUSH
+// saves p on the frame stack and maps it, POP restores it; in reverse the POP enters the child frame again with gp = 0 and
+// the PUSH pulls gp back through the map.  A type with an `out` keeps the child's value in a tape slot of its own (recorded
+// like the onion's input; the reverse pass only reads it, so vjp_replay finds it again).  Type, offset, parameter count and
+// slot are constants under StaticProgram: theta[] / gtheta[] are indexed by constants only and dissolve into registers.
+// StaticProgram only -- the interpreter has no handler.
 template <class S, class PT>
 RM_DEV void fwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
   switch (op) {
@@ -632,6 +646,27 @@ RM_DEV void fwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
 #ifdef RM_USER_COMBINATORS
     case RM_OP_USER_FOLD:  // the child's value waits on the tape for the combinator's USER_END (StaticProgram::fwd_range)
       s.st->st(s.tape0 + a0, s.d);
+      break;
+#endif
+#ifdef RM_USER_WARPS
+    case RM_OP_USER_PUSH: {  // a0 = warp type, a1 = parameter floats: child(NAME_fwd(p, theta))
+      float theta[RM_USER_WARP_MAX_PARAMS];
+#pragma unroll
+      for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i) theta[i] = (i < a1) ? P[off + i] : 0.0f;
+      s.st->st(s.sp, s.p.x); s.st->st(s.sp + 1, s.p.y); s.st->st(s.sp + 2, s.p.z);
+      s.sp += 3;
+      s.p = user_warp_fwd<S::kFast>(a0, s.p, theta);
+    } break;
+    case RM_OP_USER_POP:  // a1 = parameter floats << 16 | (value slot + 1, 0: the type has no `out`)
+      s.sp -= 3;
+      s.p = mk3(s.st->ld(s.sp), s.st->ld(s.sp + 1), s.st->ld(s.sp + 2));
+      if ((a1 & 65535) != 0) {
+        float theta[RM_USER_WARP_MAX_PARAMS];
+#pragma unroll
+        for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i) theta[i] = (i < (a1 >> 16)) ? P[off + i] : 0.0f;
+        if (s.record) s.st->st(s.tape0 + (a1 & 65535) - 1, s.d);
+        s.d = user_warp_out_fwd<S::kFast>(a0, s.d, s.p, theta);
+      }
       break;
 #endif
     default:
@@ -862,6 +897,42 @@ RM_DEV void bwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
       s.g = s.st->ld(s.tape0 + a1);
       break;
 #endif
+#ifdef RM_USER_WARPS
+    case RM_OP_USER_POP: {  // reverse order: the `out` first (s.g becomes the child's upstream), then enter the child frame
+      float theta[RM_USER_WARP_MAX_PARAMS];
+#pragma unroll
+      for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i) theta[i] = (i < (a1 >> 16)) ? P[off + i] : 0.0f;
+      if ((a1 & 65535) != 0) {
+        float gtheta[RM_USER_WARP_MAX_PARAMS];
+#pragma unroll
+        for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i) gtheta[i] = 0.0f;
+        float gd = 0.0f;
+        user_warp_out_vjp<S::kFast>(a0, s.st->ld(s.tape0 + (a1 & 65535) - 1), s.p, theta, s.g, gd, s.gp, gtheta);
+        s.g = gd;
+#pragma unroll
+        for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i)
+          if (i < (a1 >> 16)) padd(s, A + off + i, gtheta[i]);
+      }
+      s.st->st(s.sp, s.p.x); s.st->st(s.sp + 1, s.p.y); s.st->st(s.sp + 2, s.p.z);
+      s.st->st(s.sp + 3, s.gp.x); s.st->st(s.sp + 4, s.gp.y); s.st->st(s.sp + 5, s.gp.z);
+      s.sp += 6;
+      s.p = user_warp_fwd<S::kFast>(a0, s.p, theta);
+      s.gp = mk3(0.0f, 0.0f, 0.0f);
+    } break;
+    case RM_OP_USER_PUSH: {  // reverse order: leave the child frame, pull gp back through the map
+      float theta[RM_USER_WARP_MAX_PARAMS], gtheta[RM_USER_WARP_MAX_PARAMS];
+#pragma unroll
+      for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i) { theta[i] = (i < a1) ? P[off + i] : 0.0f; gtheta[i] = 0.0f; }
+      const V3 gl = s.gp;
+      s.sp -= 6;
+      s.p = mk3(s.st->ld(s.sp), s.st->ld(s.sp + 1), s.st->ld(s.sp + 2));
+      s.gp = mk3(s.st->ld(s.sp + 3), s.st->ld(s.sp + 4), s.st->ld(s.sp + 5));
+      user_warp_vjp<S::kFast>(a0, s.p, theta, gl, s.gp, gtheta);
+#pragma unroll
+      for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i)
+        if (i < a1) padd(s, A + off + i, gtheta[i]);
+    } break;
+#endif
     default:
       break;
   }
@@ -935,6 +1006,10 @@ struct StaticProgram {
     for (int i = 0; i < pc; ++i) {
       if (Code::code[i].op == RM_OP_AFFINE_PUSH) ++depth;
       if (Code::code[i].op == RM_OP_AFFINE_POP) --depth;
+#ifdef RM_USER_WARPS
+      if (Code::code[i].op == RM_OP_USER_PUSH) ++depth;      // a user warp moves the local point by whatever its map does
+      if (Code::code[i].op == RM_OP_USER_POP) --depth;
+#endif
       if (Code::code[i].op == RM_OP_CULL_MIN && depth == 0) ++k;
     }
     return (depth == 0 && k < kCullTracked) ? k : -1;
@@ -1251,6 +1326,15 @@ RM_DEV void subtree_bound(GetIns ins, const float* P, int begin, int end, float*
       // Without this case the LAST child's sphere would stay in place and bound the whole combinator.
       case RM_OP_USER_FOLD: break;
       case RM_OP_USER_END: cx = cy = cz = 0.0f; R = Ru = inf; slope = uslope = 1.0f; break;
+#endif
+#ifdef RM_USER_WARPS
+      // a user warp signs no bound (yet): nothing is known about the node, whatever its child's sphere was.  Without the POP
+      // case the child's sphere would stay in place -- expressed in the CHILD's frame, yet standing for the warped node.
+      case RM_OP_USER_PUSH:
+        if (sp >= kDepth) { overflow = true; break; }
+        st[sp].n = -2; st[sp].off = off; ++sp;
+        break;
+      case RM_OP_USER_POP: --sp; cx = cy = cz = 0.0f; R = Ru = inf; slope = uslope = 1.0f; break;
 #endif
       default: break;            // nested CULL_MIN / CULL_LSE: no effect on the bound
     }

@@ -43,7 +43,23 @@ goes to scratch memory.  The class keeps two PyTorch methods: ``combine(values [
 CPU path and the oracle of the HIP code), and a ``forward`` that evaluates the children and calls it.  A combinator signs no
 bound: no cull test covers a subtree that contains one (culling inside its children is untouched).
 
-Scenes that contain such a leaf or combinator run only through their per-scene specialised library (specialize.py), into which
+User-defined *domain operators* are the third: ``register_warp`` teaches the compiler a unary node that moves the query point
+before its one child is evaluated and, optionally, edits the value the child returns (uniform scale, mirror symmetry,
+repetition, elongation: what neither a leaf, which has no child, nor a combinator, which never sees the point, can say),
+
+    template <bool Fast> RM_DEV rm::V3 NAME_fwd(rm::V3 p, const float* theta);
+    template <bool Fast> RM_DEV void   NAME_vjp(rm::V3 p, const float* theta, rm::V3 gq, rm::V3& gp, float* gtheta);
+    template <bool Fast> RM_DEV float  NAME_out_fwd(float d, rm::V3 p, const float* theta);
+    template <bool Fast> RM_DEV void   NAME_out_vjp(float d, rm::V3 p, const float* theta, float g, float& gd, rm::V3& gp, float* gtheta);
+
+``NAME_fwd`` returns the child's query point; its VJP adds ``J_p^T gq`` to ``gp`` and writes ``gtheta[i] = gq . dq/dtheta_i``.  The
+``out`` pair is optional (both or neither, found in the source by name): the node's value from the child's value ``d``, with
+``gd = g df/dd``, ``gp += g df/dp``, ``gtheta[i] = g df/dtheta_i``.  ``p`` is the point in the node's own frame in all four.  The
+class keeps ``warp(points) -> points``, ``out(values, points) -> values`` where the source has the pair, and a ``forward`` that
+is ``out(child(warp(p)), p)``.  The field must stay a conservative distance (Lipschitz <= 1): that is the user's to see to, as
+for leaves.  A warp signs no bound: no cull test covers a subtree that contains one (culling inside its child is untouched).
+
+Scenes that contain such a leaf, combinator or warp run only through their per-scene specialised library (specialize.py), into which
 the source is compiled; the LDS interpreter has no handler for them and ``CompiledScene.lib()`` says so instead of
 rendering a wrong picture.
 """
@@ -56,7 +72,8 @@ from dataclasses import dataclass
 import torch
 import torch.nn as nn
 
-__all__ = ["register_leaf", "leaf_spec", "check_bound", "UserLeaf", "register_combinator", "combinator_spec", "UserCombinator"]
+__all__ = ["register_leaf", "leaf_spec", "check_bound", "UserLeaf", "register_combinator", "combinator_spec", "UserCombinator",
+           "register_warp", "warp_spec", "UserWarp"]
 
 
 @dataclass(frozen=True)
@@ -81,8 +98,21 @@ class UserCombinator:
     children: str       # attribute that holds the children (an nn.ModuleList or sequence of SDF modules)
 
 
+@dataclass(frozen=True)
+class UserWarp:
+    cls: type
+    name: str           # NAME of NAME_fwd / NAME_vjp (/ NAME_out_fwd / NAME_out_vjp)
+    params: tuple       # attribute names of the node's own nn.Parameters, named_parameters() order
+    hip: str
+    cost: int           # VALU estimate of the map (and the `out`) itself (compiler._cost adds the child's)
+    sha1: str
+    child: str          # attribute that holds the one child
+    has_out: bool       # the source brings NAME_out_fwd / NAME_out_vjp (and the class an ``out`` method)
+
+
 _registry: dict[type, UserLeaf] = {}
 _combinators: dict[type, UserCombinator] = {}
+_warps: dict[type, UserWarp] = {}
 
 _DEF = r"\b([A-Za-z_]\w*)_%s\s*\("
 
@@ -110,6 +140,30 @@ def _combinator_identifier(hip: str) -> str:
     if re.search(r"\basm\b|__asm", text):
         raise ValueError("a user combinator must not contain inline assembly (INTEGRATION.md: combinator contract)")
     return fwd.pop()
+
+
+def _warp_identifier(hip: str):
+    """(NAME, has_out) of a warp source.  NAME is that of the one V3-returning ``NAME_fwd``; ``NAME_vjp`` must be there, and
+    ``NAME_out_fwd`` / ``NAME_out_vjp`` come as a pair or not at all (looked up by their full names, like NAME_bound)."""
+    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
+    fwd = set(re.findall(r"RM_DEV\s+(?:rm::)?V3\s+" + _DEF % "fwd", text))
+    name = next(iter(fwd)) if len(fwd) == 1 else None
+
+    def defines(ret, fn):
+        return re.search(r"RM_DEV\s+%s\s+%s\s*\(" % (ret, re.escape(fn)), text) is not None
+
+    if name is None or not defines("void", f"{name}_vjp"):
+        raise ValueError("hip must define `template <bool Fast> RM_DEV rm::V3 NAME_fwd(rm::V3 p, const float* theta)` and `template "
+                         "<bool Fast> RM_DEV void NAME_vjp(rm::V3 p, const float* theta, rm::V3 gq, rm::V3& gp, float* gtheta)`, with "
+                         f"one NAME (found fwd: {sorted(fwd)})")
+    out_fwd, out_vjp = defines("float", f"{name}_out_fwd"), defines("void", f"{name}_out_vjp")
+    if out_fwd != out_vjp:
+        raise ValueError(f"hip may define `template <bool Fast> RM_DEV float {name}_out_fwd(float d, rm::V3 p, const float* theta)` and "
+                         f"`template <bool Fast> RM_DEV void {name}_out_vjp(float d, rm::V3 p, const float* theta, float g, float& gd, "
+                         f"rm::V3& gp, float* gtheta)`: both or neither (found {name}_out_fwd: {out_fwd}, {name}_out_vjp: {out_vjp})")
+    if re.search(r"\basm\b|__asm", text):
+        raise ValueError("a user warp must not contain inline assembly (INTEGRATION.md: warp contract)")
+    return name, out_fwd
 
 
 def _has_bound(hip: str, name: str) -> bool:
@@ -184,11 +238,13 @@ def register_leaf(cls, *, params, hip: str, cost: int):
         if (old.sha1, old.params, old.cost) != (spec.sha1, spec.params, spec.cost):
             raise ValueError(f"register_leaf: {cls.__name__} is already registered with different source, parameters or cost")
         return cls
-    for other in list(_registry.values()) + list(_combinators.values()):
+    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()):
         if other.name == spec.name:          # (the user types of one scene are compiled into one translation unit)
             raise ValueError(f"register_leaf: the identifier {spec.name!r} is already used by {other.cls.__name__}")
     if _registered_class(cls, _combinators) is not None:
         raise TypeError(f"register_leaf: {cls.__name__} is already registered as a combinator")
+    if _registered_class(cls, _warps) is not None:
+        raise TypeError(f"register_leaf: {cls.__name__} is already registered as a warp")
     cls._rm_torch_forward = _torch_forward(cls)
     cls.forward = _device_forward
     _registry[cls] = spec
@@ -239,7 +295,9 @@ def register_combinator(cls, *, params=(), hip: str, cost: int = 4, children: st
         return cls
     if _registered_class(cls) is not None:
         raise TypeError(f"register_combinator: {cls.__name__} is already registered as a leaf")
-    for other in list(_registry.values()) + list(_combinators.values()):
+    if _registered_class(cls, _warps) is not None:
+        raise TypeError(f"register_combinator: {cls.__name__} is already registered as a warp")
+    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()):
         if other.name == spec.name:
             raise ValueError(f"register_combinator: the identifier {spec.name!r} is already used by {other.cls.__name__}")
     cls._rm_torch_forward = _torch_forward(cls)
@@ -263,6 +321,73 @@ def combinator_children(node, spec: UserCombinator):
     if not kids or not all(isinstance(k, nn.Module) for k in kids):
         raise ValueError(f"{type(node).__name__}: the children attribute {spec.children!r} must hold at least one SDF module")
     return kids
+
+
+def register_warp(cls, *, params=(), hip: str, cost: int = 10, child: str = "sdf"):
+    """Make ``cls`` (an ``nn.Module`` subclass) compilable as a unary scene node that evaluates its child at ``warp(p)`` and,
+    where it has an ``out``, returns ``out(child value, p)``.
+
+    params: names of the node's OWN ``nn.Parameter`` attributes in ``named_parameters()`` order (may be empty); a module's own
+            parameters precede its child's, so they are contiguous in the scene block.
+    hip:    source of NAME_fwd / NAME_vjp and, optionally, NAME_out_fwd / NAME_out_vjp (module docstring).
+    cost:   VALU instructions of the map and the ``out``, roughly; the child's are added by the compiler.
+    child:  the attribute that holds the one child, an SDF module.
+
+    ``cls`` has ``warp(self, points [..., 3]) -> [..., 3]``, ``out(self, values [..., 1], points [..., 3]) -> [..., 1]`` exactly when
+    the source has the ``out`` pair, and a ``forward(self, query_coords)`` that composes them around the child.  Registration
+    installs the same dispatch as ``register_leaf``: CUDA points go to the HIP evaluator, anything else to the class's own
+    forward (kept under ``_rm_torch_forward``).  Registering a class again with the same source is a no-op; with other source,
+    parameters, cost or child attribute it is an error.  Identifiers are unique across leaves, combinators and warps."""
+    if not (isinstance(cls, type) and issubclass(cls, nn.Module)):
+        raise TypeError(f"register_warp: {cls!r} is not an nn.Module subclass")
+    if getattr(cls, "_rm_kind", None) is not None:
+        raise TypeError(f"register_warp: {cls.__name__} is already a ray_marching_amd node")
+    if _registered_class(cls) is not None:
+        raise TypeError(f"register_warp: {cls.__name__} is already registered as a leaf")
+    if _registered_class(cls, _combinators) is not None:
+        raise TypeError(f"register_warp: {cls.__name__} is already registered as a combinator")
+    if not callable(getattr(cls, "warp", None)):
+        raise TypeError(f"register_warp: {cls.__name__} has no warp(points [..., 3]) -> [..., 3] method")
+    if not isinstance(child, str) or not child:
+        raise ValueError("register_warp: child must name the attribute that holds the child module")
+    params = tuple(params)
+    if not all(isinstance(p, str) for p in params) or len(set(params)) != len(params):
+        raise ValueError("register_warp: params must be distinct attribute names")
+    name, has_out = _warp_identifier(hip)
+    if has_out != callable(getattr(cls, "out", None)):
+        raise TypeError(f"register_warp: {cls.__name__} " + (
+            f"has no out(values, points) method, but its source defines {name}_out_fwd / {name}_out_vjp" if has_out else
+            f"has an out(values, points) method, but its source defines no {name}_out_fwd / {name}_out_vjp"))
+    spec = UserWarp(cls, name, params, hip, int(cost), hashlib.sha1(hip.encode()).hexdigest(), child, has_out)
+    if spec.cost < 0:
+        raise ValueError("register_warp: cost must be >= 0")
+    old = _warps.get(cls)
+    if old is not None:
+        if (old.sha1, old.params, old.cost, old.child) != (spec.sha1, spec.params, spec.cost, spec.child):
+            raise ValueError(f"register_warp: {cls.__name__} is already registered with different source, parameters, cost or "
+                             "child attribute")
+        return cls
+    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()):
+        if other.name == spec.name:
+            raise ValueError(f"register_warp: the identifier {spec.name!r} is already used by {other.cls.__name__}")
+    cls._rm_torch_forward = _torch_forward(cls)
+    cls.forward = _device_forward
+    _warps[cls] = spec
+    return cls
+
+
+def warp_spec(node):
+    """The warp registration of this module's class (or of the registered class it derives from), or None."""
+    c = _registered_class(type(node), _warps)
+    return None if c is None else _warps[c]
+
+
+def warp_child(node, spec: UserWarp):
+    """The one child of a warp instance."""
+    kid = getattr(node, spec.child, None)
+    if not isinstance(kid, nn.Module):
+        raise ValueError(f"{type(node).__name__}: the child attribute {spec.child!r} is missing or not an SDF module")
+    return kid
 
 
 def leaf_parameters(node, spec):

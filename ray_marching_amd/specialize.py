@@ -22,8 +22,8 @@ Policy (env RM_SPECIALIZE):
   "jit"      build a missing library synchronously on first use (3-14 s of hipcc);
   "off"      always interpret.
 
-Scenes with user-defined leaves or combinators (extensions.register_leaf / register_combinator; their HIP source is compiled
-into the library) have no
+Scenes with user-defined leaves, combinators or warps (extensions.register_leaf / register_combinator / register_warp; their
+HIP source is compiled into the library) have no
 interpreter to start on: "auto" and "jit" both build a missing library synchronously on first use, "prebuilt" and
 "off" raise RmError (load_user).
 """
@@ -137,15 +137,43 @@ def _combinator_section(cs: CompiledScene) -> str:
         "  switch (type) {\n" + cases_v + "    default: break;\n  }\n}\n")
 
 
+def _warp_section(cs: CompiledScene) -> str:
+    """User warp sources and the dispatch over the warp type (RM_OP_USER_PUSH / _POP: aux0), for the same first inclusion as
+    the leaf and combinator sections and independent of both.  The `out` switches list the types that bring one."""
+    types = cs.user_warps
+    cases_f = "".join(f"    case {t}: return {name}_fwd<Fast>(p, theta);\n" for t, (name, _, _, _) in enumerate(types))
+    cases_v = "".join(f"    case {t}: {name}_vjp<Fast>(p, theta, gq, gp, gtheta); break;\n" for t, (name, _, _, _) in enumerate(types))
+    cases_of = "".join(f"    case {t}: return {name}_out_fwd<Fast>(d, p, theta);\n" for t, (name, _, out, _) in enumerate(types) if out)
+    cases_ov = "".join(f"    case {t}: {name}_out_vjp<Fast>(d, p, theta, g, gd, gp, gtheta); break;\n"
+                       for t, (name, _, out, _) in enumerate(types) if out)
+    sources = "".join(f"// user warp {t}: {name}, {n} parameter floats, {'with' if out else 'no'} out, sha1 {sha}\n{src.strip()}\n"
+                      for t, ((name, n, out, sha), src) in enumerate(zip(types, cs.user_warp_sources)))
+    return (
+        f"#define RM_USER_WARPS {len(types)}\n"
+        f"#define RM_USER_WARP_MAX_PARAMS {max(1, max(n for _, n, _, _ in types))}\n"
+        + sources +
+        "template <bool Fast> RM_DEV V3 user_warp_fwd(int type, V3 p, const float* theta) {\n"
+        "  switch (type) {\n" + cases_f + "    default: return mk3(__builtin_nanf(\"\"), __builtin_nanf(\"\"), __builtin_nanf(\"\"));\n  }\n}\n"
+        "template <bool Fast> RM_DEV void user_warp_vjp(int type, V3 p, const float* theta, V3 gq, V3& gp, float* gtheta) {\n"
+        "  switch (type) {\n" + cases_v + "    default: break;\n  }\n}\n"
+        "template <bool Fast> RM_DEV float user_warp_out_fwd(int type, float d, V3 p, const float* theta) {\n"
+        "  switch (type) {\n" + cases_of + "    default: return __builtin_nanf(\"\");\n  }\n}\n"
+        "template <bool Fast> RM_DEV void user_warp_out_vjp(int type, float d, V3 p, const float* theta, float g, float& gd, V3& gp, "
+        "float* gtheta) {\n"
+        "  switch (type) {\n" + cases_ov + "    default: break;\n  }\n}\n")
+
+
 def user_names(cs: CompiledScene):
     """(names, what) of the user types of a scene, for messages: leaf-only scenes read as they always did."""
-    leaves = [name for name, _, _ in cs.user_leaves]
-    combs = list(dict.fromkeys(name for name, _, _, _ in cs.user_combinators))
-    if not combs:
-        return ", ".join(leaves), "leaves"
-    if not leaves:
-        return ", ".join(combs), "combinators"
-    return "leaves: " + ", ".join(leaves) + "; combinators: " + ", ".join(combs), "leaves and combinators"
+    kinds = [("leaves", [name for name, _, _ in cs.user_leaves]),
+             ("combinators", list(dict.fromkeys(name for name, _, _, _ in cs.user_combinators))),
+             ("warps", [name for name, _, _, _ in cs.user_warps])]
+    kinds = [(what, names) for what, names in kinds if names]
+    if len(kinds) <= 1:
+        what, names = kinds[0] if kinds else ("leaves", [])
+        return ", ".join(names), what
+    whats = [what for what, _ in kinds]
+    return "; ".join(f"{what}: " + ", ".join(names) for what, names in kinds), ", ".join(whats[:-1]) + " and " + whats[-1]
 
 
 def code_header(cs: CompiledScene) -> str:
@@ -159,9 +187,10 @@ def code_header(cs: CompiledScene) -> str:
     # included twice: by csrc/rm_device.h in front of the handlers (RM_STATIC_CODE_LEAVES: the user leaves only), then by
     # csrc/rm_abi.hip for the program
     head = "// generated by ray_marching_amd/specialize.py -- scene program as a compile-time constant\n"
-    if not cs.user_leaves and not cs.user_combinators:
+    if not cs.user_leaves and not cs.user_combinators and not cs.user_warps:
         return head + "#ifndef RM_STATIC_CODE_LEAVES\n" + program + "#endif\n"
-    user = (_leaf_section(cs) if cs.user_leaves else "") + (_combinator_section(cs) if cs.user_combinators else "")
+    user = ((_leaf_section(cs) if cs.user_leaves else "") + (_combinator_section(cs) if cs.user_combinators else "")
+            + (_warp_section(cs) if cs.user_warps else ""))
     return head + "#ifdef RM_STATIC_CODE_LEAVES\n" + user + "#else\n" + program + "#endif\n"
 
 
@@ -213,7 +242,7 @@ def build(cs: CompiledScene, force: bool = False, precision: str = "exact") -> s
     if not static_backward(cs):
         cmd.append("-DRM_NO_BACKWARD")
     cmd += [os.path.join(CSRC, "rm_abi.hip"), "-o", tmp]
-    if not cs.user_leaves and not cs.user_combinators:
+    if not cs.user_leaves and not cs.user_combinators and not cs.user_warps:
         subprocess.run(cmd, check=True, cwd=CSRC)
     else:
         # user source goes through the compiler here: its diagnostics belong in the exception, and the frame kernel's
@@ -352,7 +381,7 @@ def ensure(module_or_cs):
 def default_scenes():
     from .scene import scene_registry as R
     from .scene.primitives import SDFSphere
-    from .contrib import make_carved_scene, make_link_scene
+    from .contrib import make_carved_scene, make_link_scene, make_warped_scene
     return {
         "link_scene": make_link_scene(),
         "bounded_link_scene": make_link_scene(bounded=True),
@@ -362,6 +391,7 @@ def default_scenes():
         "make_closed_test_scene": R.make_closed_test_scene(),
         "make_many_primitive_scene32": R.make_many_primitive_scene(32),
         "carved_scene": make_carved_scene(),
+        "warped_scene": make_warped_scene(),
     }
 
 
