@@ -181,7 +181,13 @@ typedef struct RmTetra {
 /* shader modes, order of rendering/shader.py:204-209 */
 enum {
   RM_MODE_LAMBERTIAN = 0, RM_MODE_DISTANCE = 1, RM_MODE_PROXIMITY = 2, RM_MODE_VIGNETTE = 3,
-  RM_MODE_NORMAL = 4, RM_MODE_LAPLACIAN = 5, RM_MODE_TANGENT = 6, RM_MODE_SPIN = 7
+  RM_MODE_NORMAL = 4, RM_MODE_LAPLACIAN = 5, RM_MODE_TANGENT = 6, RM_MODE_SPIN = 7,
+  RM_MODE_USER = 8         /* a user-defined per-pixel shader (extensions.register_shader): NAME_fwd / NAME_vjp of the ONE shader whose
+                              HIP source was compiled into this library, theta = the floats that follow the scene's own in the
+                              parameter block.  Accepted by rm_render_forward / rm_render_backward of a library that reports
+                              rm_user_shaders() == 1 and refused by every other; rm_shade_forward / rm_shade_backward, which have no
+                              scene and hence no theta, never take it.  Per pixel, [.., 3] like the other ungrouped modes (no global
+                              normalisation, no colormap); the frame evaluates neither the Laplacian nor scene(p) for it */
 };
 
 /* flags */
@@ -239,6 +245,9 @@ int rm_user_combinators(void);
 /* ... and the number of user warp types (RM_OP_USER_PUSH / RM_OP_USER_POP handlers; extensions.register_warp): 0 for the generic
  * libraries and for every library of a scene without warps. */
 int rm_user_warps(void);
+/* ... and whether a user shader (RM_MODE_USER; extensions.register_shader) was compiled in: 1 for the library of a (scene, shader)
+ * pair, 0 for every other. */
+int rm_user_shaders(void);
 
 /* Workspace sizing for the backward entry points: number of floats of
  * `partials` needed for a launch over n rays. */

@@ -45,6 +45,7 @@ def dtype_code(dtype) -> int:
 WORK_WORDS = 64 + 64 * 32 + 8 * 4 * 32 + 64 * 32   # RM_WORK_WORDS (min/max words, tile queues, parking counters, min/max slots)
 CAMERA_BWD_BLOCKS = 256     # RM_CAMERA_BWD_BLOCKS
 NORM_BWD_BLOCKS = 1024      # RM_NORM_BWD_BLOCKS
+MODE_USER = 8               # RM_MODE_USER: a user-defined shader (extensions.register_shader); not one of MODES
 MODES = ("lambertian", "distance", "proximity", "vignette", "normal", "laplacian", "tangent", "spin")
 
 
@@ -75,6 +76,7 @@ _SIGNATURES = {
     "rm_user_leaves": (C.c_int, []),
     "rm_user_combinators": (C.c_int, []),
     "rm_user_warps": (C.c_int, []),
+    "rm_user_shaders": (C.c_int, []),
     "rm_grad_partials_floats": (C.c_int64, [C.POINTER(RmScene), C.c_int64]),
     "rm_validate_program": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rm_sdf_forward": (C.c_int, [C.POINTER(RmScene), _P, _P, C.c_int64, C.c_int32, _P]),

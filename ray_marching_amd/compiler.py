@@ -117,6 +117,9 @@ class CompiledScene:
     user_combinator_sources: tuple = () # the HIP source of every combinator CLASS among them (one text per identifier)
     user_warps: tuple = ()              # (identifier, parameter floats, has an `out`, sha1) per user warp type, in aux0 order
     user_warp_sources: tuple = ()       # their HIP source texts
+    user_shader: tuple = ()             # (identifier, parameter floats, sha1) of the user shader of a (scene, shader) program, else ()
+    user_shader_source: str = ""        # its HIP source text
+    shader_offset: int = 0              # where its theta starts in the block (= the scene's own n_params)
     _device_programs: dict = field(default_factory=dict)
     _table: dict = field(default_factory=dict)
     _leaf_sizes: object = None
@@ -136,7 +139,7 @@ class CompiledScene:
         scenes with many parameters always uses the generic library (accumulators in LDS).
         ``precision="fast"`` selects the opt-in fast-arithmetic builds."""
         from . import specialize
-        if self.user_leaves or self.user_combinators or self.user_warps:
+        if self.user_leaves or self.user_combinators or self.user_warps or self.user_shader:
             return self._user_leaf_lib(backward, precision)
         generic = _abi.generic_lib(precision)
         if backward and not specialize.static_backward(self):
@@ -150,8 +153,8 @@ class CompiledScene:
         return self._lib
 
     def _user_leaf_lib(self, backward: bool, precision: str):
-        """Scenes with user-defined leaves, combinators or warps (RM_OP_USER*) exist only as specialised kernels: the interpreter has no
-        handler for them, so everything that would fall back to it raises instead."""
+        """Scenes with user-defined leaves, combinators or warps (RM_OP_USER*) and (scene, shader) programs (RM_MODE_USER) exist only as
+        specialised kernels: the interpreter has no handler for them, so everything that would fall back to it raises instead."""
         from . import specialize
         names, what = specialize.user_names(self)
         if backward and not specialize.static_backward(self):
@@ -169,6 +172,8 @@ class CompiledScene:
                                f"{len(self.user_combinators)}")
         if lib.rm_user_warps() != len(self.user_warps):
             raise _abi.RmError(f"{lib._name} was built with {lib.rm_user_warps()} user warp types, the scene has {len(self.user_warps)}")
+        if lib.rm_user_shaders() != len(self.user_shader[:1]):
+            raise _abi.RmError(f"{lib._name} was built with {lib.rm_user_shaders()} user shaders, the program has {len(self.user_shader[:1])}")
         if precision == "exact":
             self._lib = lib
         return lib
@@ -483,8 +488,9 @@ def _emit(node, em: _Emitter, n_params: int):
             "for the HIP kernels")
 
 
-def compile_scene(module: nn.Module) -> CompiledScene:
-    """Lower an SDF module tree.  Pure host logic (no GPU needed)."""
+def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
+    """Lower an SDF module tree.  Pure host logic (no GPU needed).  ``shader``: an instance of a class registered with
+    extensions.register_shader; its parameters follow the scene's in the block (compiled_with_shader)."""
     names, leaves, offsets, table = [], [], [], {}
     cursor = 0
     for name, p in module.named_parameters():
@@ -493,7 +499,21 @@ def compile_scene(module: nn.Module) -> CompiledScene:
         offsets.append(cursor)
         table[id(p)] = cursor
         cursor += p.numel()
-    n_params = cursor
+    shader_offset, user_shader, shader_source = cursor, (), ""
+    if shader is not None:
+        from .extensions import shader_parameters, shader_spec
+        spec = shader_spec(shader)
+        if spec is None:
+            raise TypeError(f"{type(shader).__name__} is not a registered shader (extensions.register_shader)")
+        for name, p in zip(spec.params, shader_parameters(shader, spec)):
+            if id(p) in table:
+                raise ValueError(f"{type(shader).__name__}.{name} is also a parameter of the scene (shared parameters are not supported)")
+            names.append("shader." + name)
+            leaves.append(p)
+            offsets.append(cursor)
+            cursor += p.numel()
+        user_shader, shader_source = (spec.name, cursor - shader_offset, spec.sha1), spec.hip
+    n_params = cursor                 # (derived constants start behind the shader's floats)
     em = _Emitter(table)
     # derived block = [capsule constants of every SDFLine (gradients flow through them) | cull bounds, bound tables]
     em.n_grad_derived = em.n_derived = 6 * sum(1 for m in module.modules() if getattr(m, "_rm_kind", None) == "line")
@@ -517,12 +537,15 @@ def compile_scene(module: nn.Module) -> CompiledScene:
     user_warps = tuple((u.name, em.warp_floats[t], u.has_out, u.sha1) for t, u in enumerate(em.warp_types))
     if user_warps:
         signature = signature + ((),) * (8 - len(signature)) + (user_warps,)      # (signature[-3], [-2] stay leaves, combinators)
+    if user_shader:
+        signature = signature + ((),) * (9 - len(signature)) + (user_shader,)     # (signature[6:9] stay leaves, combinators, warps)
     return CompiledScene(program=program, leaves=leaves, leaf_names=names, leaf_offsets=offsets,
                          n_params=n_params, n_derived=em.n_derived, n_grad_derived=em.n_grad_derived, stack_floats=em.max_depth,
                          n_slots=em.n_slots, signature=signature, user_leaves=user_leaves,
                          user_sources=tuple(u.hip for u in em.user_types), user_bounded=tuple(u.bounded for u in em.user_types),
                          user_combinators=user_combinators, user_combinator_sources=comb_sources,
-                         user_warps=user_warps, user_warp_sources=tuple(u.hip for u in em.warp_types))
+                         user_warps=user_warps, user_warp_sources=tuple(u.hip for u in em.warp_types),
+                         user_shader=user_shader, user_shader_source=shader_source, shader_offset=shader_offset)
 
 
 def structure_key(module: nn.Module):
@@ -551,4 +574,30 @@ def compiled_for(module: nn.Module) -> CompiledScene:
     if cache is None or cache[0] != key:
         cache = (key, compile_scene(module))
         _compiled[module] = cache
+    return cache[1]
+
+
+_with_shader = weakref.WeakKeyDictionary()   # scene -> WeakKeyDictionary(shader -> (structure keys, CompiledScene))
+
+
+def compiled_with_shader(module: nn.Module, shader: nn.Module) -> CompiledScene:
+    """The program of ``module`` shaded by ``shader`` (an instance of a class registered with extensions.register_shader):
+    the scene's instructions, with the shader's parameters behind the scene's in ``leaves`` / ``leaf_names`` /
+    ``leaf_offsets`` and ``n_params`` grown by their floats, so that the prologue gathers theta with the scene's parameters
+    and its gradients leave through the scene's accumulators.  The derived constants keep starting at ``n_params``: the
+    instruction fields that point into the derived block (capsule constants, cull bounds, bound tables) move up by
+    the shader's floats (a bound table to the next multiple of 4) and every other field is the scene's, row for row.
+    Cached weakly per (scene, shader) pair and recompiled when the topology of either changes, like compiled_for."""
+    base = compiled_for(module)
+    key = (structure_key(module), structure_key(shader))
+    per_scene = _with_shader.get(module)
+    if per_scene is None:
+        per_scene = _with_shader[module] = weakref.WeakKeyDictionary()
+    cache = per_scene.get(shader)
+    if cache is None or cache[0] != key:
+        cs = compile_scene(module, shader)
+        if cs.program.shape != base.program.shape or not np.array_equal(cs.program[:, 0], base.program[:, 0]):
+            raise AssertionError("compiled_with_shader: the instructions differ from the scene's own program")
+        cache = (key, cs)
+        per_scene[shader] = cache
     return cache[1]

@@ -1,13 +1,13 @@
-"""Leaves, combinators and domain operators beyond the reference's vocabulary, added through the public extension point
-(extensions.register_leaf / register_combinator / register_warp) exactly as a user would add their own: a PyTorch ``forward`` /
-``combine`` / ``warp`` (the CPU path and the oracle) and the same op stream in HIP."""
+"""Leaves, combinators, domain operators and shaders beyond the reference's vocabulary, added through the public extension point
+(extensions.register_leaf / register_combinator / register_warp / register_shader) exactly as a user would add their own: a
+PyTorch ``forward`` / ``combine`` / ``warp`` (the CPU path and the oracle) and the same op stream in HIP."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
-from .extensions import register_combinator, register_leaf, register_warp
+from .extensions import register_combinator, register_leaf, register_shader, register_warp
 
 
 class SDFLink(nn.Module):
@@ -395,3 +395,112 @@ def make_warped_scene():
         SDFIntersection([SDFRepeat(SDFSphere(radius=0.12), period=(0.5, 0.5, 0.5)),
                          A(SDFBox(halfsides=(1.2, 0.2, 1.2)), orientation=ident, translation=[0.0, -1.4, 0.0])]),
     ])
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# Per-pixel shaders (extensions.register_shader): what lights a user's solid, with parameters of its own to optimise
+# --------------------------------------------------------------------------------------------------------------------
+class DirectionalLightShader(nn.Module):
+    """A distant light and a coloured surface: ``rgb = albedo * (ambient + (1 - ambient) * clamp(n . l / |l|, 0, 1))``.  Seven
+    parameter floats (``light_direction`` [3], ``albedo`` [3], ``ambient``); reads only the normal."""
+
+    def __init__(self, light_direction=(0.0, 0.0, -1.0), albedo=(1.0, 1.0, 1.0), ambient: float = 0.1) -> None:
+        super().__init__()
+        self.light_direction = nn.Parameter(torch.tensor(light_direction, dtype=torch.float32))
+        self.albedo = nn.Parameter(torch.tensor(albedo, dtype=torch.float32))
+        self.ambient = nn.Parameter(torch.tensor(ambient, dtype=torch.float32))
+
+    def forward(self, px_coords: Tensor, camera_orientation: Tensor, pixel_frames: Tensor, ray_directions: Tensor,
+                surface_coords: Tensor, surface_normals: Tensor) -> Tensor:
+        light = self.light_direction / torch.linalg.vector_norm(self.light_direction)
+        c = (surface_normals * light).sum(dim=-1, keepdim=True).clamp(0, 1)
+        return self.albedo * (self.ambient + (1 - self.ambient) * c)
+
+
+# theta = {light_direction[3], albedo[3], ambient}; the forward restates the ATen op stream above (vector_norm: norm3, mul().sum(-1):
+# dot_seq, clamp: t_clamp, every product and sum rounded on its own), the VJP is autograd's, written out
+_DIRECTIONAL_HIP = r"""
+template <bool Fast> RM_DEV rm::V3 directional_light_fwd(const rm::ShadeIn& s, const float* theta) {
+  const rm::V3 L = mk3(theta[0], theta[1], theta[2]);
+  const float ln = norm3(L);
+  const rm::V3 l = mk3(L.x / ln, L.y / ln, L.z / ln);
+  const float c = t_clamp(dot_seq(s.n, l), 0.0f, 1.0f);
+  const float k = theta[6] + (1.0f - theta[6]) * c;
+  return mk3(theta[3] * k, theta[4] * k, theta[5] * k);
+}
+template <bool Fast> RM_DEV void directional_light_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 g, rm::ShadeGrad& gs, float* gtheta) {
+  const rm::V3 L = mk3(theta[0], theta[1], theta[2]);
+  const float ln = norm3_t<Fast>(L);
+  const rm::V3 l = mk3(div_t<Fast>(L.x, ln), div_t<Fast>(L.y, ln), div_t<Fast>(L.z, ln));
+  const float d = dot_seq(s.n, l);
+  const float c = t_clamp(d, 0.0f, 1.0f);
+  const float k = theta[6] + (1.0f - theta[6]) * c;
+  gtheta[3] = g.x * k; gtheta[4] = g.y * k; gtheta[5] = g.z * k;
+  const float gk = (g.x * theta[3] + g.y * theta[4]) + g.z * theta[5];
+  gtheta[6] = gk - gk * c;
+  const float gc = gk * (1.0f - theta[6]);
+  const float gd = (d >= 0.0f && d <= 1.0f) ? gc : 0.0f;       // clamp passes the gradient on the closed interval
+  gs.n = gs.n + gd * l;
+  // l = L / |L|: dL = (gl - l (gl . l)) / |L|
+  const rm::V3 gl = gd * s.n;
+  const float gll = dot_seq(gl, l);
+  gtheta[0] = div_t<Fast>(gl.x - l.x * gll, ln);
+  gtheta[1] = div_t<Fast>(gl.y - l.y * gll, ln);
+  gtheta[2] = div_t<Fast>(gl.z - l.z * gll, ln);
+}
+"""
+
+register_shader(DirectionalLightShader, params=("light_direction", "albedo", "ambient"), hip=_DIRECTIONAL_HIP)
+
+
+class DepthCueShader(nn.Module):
+    """The Lambertian term ``c = clamp(-(v . n), 0, 1)`` fading into ``far_colour`` with the distance the ray travelled:
+    ``rgb = w * c + (1 - w) * far_colour``, ``w = 1 / (1 + density * |o - p|)``.  Four parameter floats (``density``,
+    ``far_colour`` [3]); reads the ray origin, the surface point, the direction and the normal.  No transcendental function."""
+
+    def __init__(self, density: float = 0.25, far_colour=(0.5, 0.6, 0.7)) -> None:
+        super().__init__()
+        self.density = nn.Parameter(torch.tensor(density, dtype=torch.float32))
+        self.far_colour = nn.Parameter(torch.tensor(far_colour, dtype=torch.float32))
+
+    def forward(self, px_coords: Tensor, camera_orientation: Tensor, pixel_frames: Tensor, ray_directions: Tensor,
+                surface_coords: Tensor, surface_normals: Tensor) -> Tensor:
+        c = (ray_directions * surface_normals).sum(dim=-1, keepdim=True).neg().clamp(0, 1)
+        dist = torch.linalg.vector_norm(px_coords - surface_coords, dim=-1, keepdim=True)
+        w = (self.density * dist + 1).reciprocal()
+        return w * c + (1 - w) * self.far_colour
+
+
+# theta = {density, far_colour[3]}
+_DEPTH_CUE_HIP = r"""
+template <bool Fast> RM_DEV rm::V3 depth_cue_fwd(const rm::ShadeIn& s, const float* theta) {
+  const float c = t_clamp(-dot_seq(s.v, s.n), 0.0f, 1.0f);
+  const float dist = norm3(s.o - s.p);
+  const float w = 1.0f / (theta[0] * dist + 1.0f);
+  const float wc = w * c, u = 1.0f - w;
+  return mk3(wc + u * theta[1], wc + u * theta[2], wc + u * theta[3]);
+}
+template <bool Fast> RM_DEV void depth_cue_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 g, rm::ShadeGrad& gs, float* gtheta) {
+  const float e = -dot_seq(s.v, s.n);
+  const float c = t_clamp(e, 0.0f, 1.0f);
+  const rm::V3 d = s.o - s.p;
+  const float dist = norm3_t<Fast>(d);
+  const float w = div_t<Fast>(1.0f, theta[0] * dist + 1.0f);
+  const float u = 1.0f - w;
+  gtheta[1] = g.x * u; gtheta[2] = g.y * u; gtheta[3] = g.z * u;
+  const float gsum = (g.x + g.y) + g.z;
+  const float gw = gsum * c - ((g.x * theta[1] + g.y * theta[2]) + g.z * theta[3]);
+  const float gu = -(gw * (w * w));                            // w = 1 / u', u' = density * dist + 1
+  gtheta[0] = gu * dist;
+  const float gdist = gu * theta[0];
+  const float sc = (dist == 0.0f) ? 0.0f : div_t<Fast>(gdist, dist);   // norm backward: self * (grad / norm), 0 where norm == 0
+  const rm::V3 gd = sc * d;
+  gs.o = gs.o + gd;
+  gs.p = gs.p - gd;
+  const float ge = (e >= 0.0f && e <= 1.0f) ? gsum * w : 0.0f;  // clamp passes the gradient on the closed interval
+  gs.v = gs.v - ge * s.n;
+  gs.n = gs.n - ge * s.v;
+}
+"""
+
+register_shader(DepthCueShader, params=("density", "far_colour"), hip=_DEPTH_CUE_HIP)

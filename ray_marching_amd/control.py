@@ -9,6 +9,7 @@ pyautogui (the reference's control.py does, at import time: control.py:3-4,14).
 """
 from __future__ import annotations
 
+import numbers
 import os
 
 import torch
@@ -16,12 +17,28 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import _abi, ops
-from .compiler import compiled_for
+from .compiler import compiled_for, compiled_with_shader
 from .rendering.ray_marching import PinholeCamera, SDFMarcher, SDFNormals
 from .rendering.shader import Shader
 
 
 _AB_PACK = bool(os.environ.get("RM_AB_PACK"))      # experiment knob: pack the parameters for inference frames too
+
+
+def resolve_mode(scene, mode, precision: str = "exact"):
+    """(kernel mode, CompiledScene) of a ``mode`` argument: an integer is one of the reference's eight shaders (``mode % 8``) on the
+    scene's own program; an instance of a class registered with extensions.register_shader is RM_MODE_USER on the program of
+    the (scene, shader) pair, whose library is resolved here, on the host, before any device work (it exists only as a
+    specialised build: RM_SPECIALIZE=off / prebuilt without it raise RmError)."""
+    if isinstance(mode, numbers.Integral):
+        return int(mode) % 8, compiled_for(scene)
+    from .extensions import shader_spec
+    if not isinstance(mode, nn.Module) or shader_spec(mode) is None:
+        raise TypeError(f"mode must be an int (one of the eight built-in shaders) or an instance of a class registered with "
+                        f"extensions.register_shader, not {type(mode).__name__}")
+    cs = compiled_with_shader(scene, mode)
+    cs.lib(False, precision)
+    return _abi.MODE_USER, cs
 
 
 class CapturedFrame:
@@ -39,11 +56,11 @@ class CapturedFrame:
                  display: bool = False):
         """``display=True``: the replay writes main.py:78-84's display tensor ([H,W,4] fp32, alpha 1: RenderLoop.display_frame)
         instead of the [N,H,W,3] image (one camera)."""
-        self.loop, self.mode, self.degree, self.steps, self.rows = loop, mode % 8, int(degree), int(marching_steps), rows
+        self.mode, self.cs = resolve_mode(loop.scene, mode, loop.precision)
+        self.loop, self.degree, self.steps, self.rows = loop, int(degree), int(marching_steps), rows
         self.display = bool(display)
         rp, rd = loop._io_buffers(False)
         dev, n = rp.device, rp.shape[0]
-        self.cs = compiled_for(loop.scene)
         self.q = torch.zeros(n, 4, dtype=rp.dtype, device=dev)
         self.q[:, 0] = 1.0
         self.t = torch.zeros(n, 3, dtype=rp.dtype, device=dev)
@@ -370,11 +387,11 @@ class RenderLoop(nn.Module):
                                                         _abi.ptr(st["scratch"]), stream), "rm_tile_order_from_cost")
         st["valid"] = True
 
-    def capture(self, mode: int = 0, degree: int = 1, marching_steps: int = 32, rows=None, display: bool = False) -> CapturedFrame:
+    def capture(self, mode=0, degree: int = 1, marching_steps: int = 32, rows=None, display: bool = False) -> CapturedFrame:
         """HIP-graph replay of one inference frame (see CapturedFrame); ``display=True``: of the [H,W,4] display tensor."""
         return CapturedFrame(self, mode, degree, marching_steps, rows, display)
 
-    def training_step(self, loss_fn, mode: int = 0, degree: int = 1, marching_steps: int = 32, optimizer=None,
+    def training_step(self, loss_fn, mode=0, degree: int = 1, marching_steps: int = 32, optimizer=None,
                       pose_requires_grad: bool = False):
         """forward -> ``loss_fn(image)`` -> backward (-> ``optimizer.step()``) captured into ONE HIP graph on first use
         and replayed from then on (graphs.CapturedTrainingStep): ``step = loop.training_step(loss_fn, ...)``, then
@@ -383,7 +400,7 @@ class RenderLoop(nn.Module):
         from .graphs import CapturedTrainingStep
         return CapturedTrainingStep(self, loss_fn, mode, degree, marching_steps, optimizer, pose_requires_grad)
 
-    def display_frame(self, orientations: Tensor, translations: Tensor, mode: int = 0, degree: int = 1,
+    def display_frame(self, orientations: Tensor, translations: Tensor, mode=0, degree: int = 1,
                       marching_steps: int = 32) -> Tensor:
         """What main.py:78-84 hands to ``Window.draw`` -- ``F.pad(images.mean(dim=0).float(), [0, 1], value=1.0)``:
         contiguous [H, W, 4] float32, alpha 1 (torchwindow/window.py:146-174) -- written by the frame kernel itself
@@ -393,21 +410,22 @@ class RenderLoop(nn.Module):
             return self.forward(orientations, translations, mode, degree, marching_steps, _image_dtype="rgba")
 
     @torch.compiler.disable      # main.py:44 wraps the loop in torch.compile: Dynamo steps over the ctypes launches (eager bits, no Inductor kernel)
-    def forward(self, orientations: Tensor, translations: Tensor, mode: int = 0, degree: int = 1,
+    def forward(self, orientations: Tensor, translations: Tensor, mode=0, degree: int = 1,
                 marching_steps: int = 32, rows=None, allreduce_minmax=None, tile_order=None, tile_cost=None,
                 _image_dtype=None):
         """-> image [N, H, W, 3] in the module's dtype (modes 6, 7: promoted with the colormap's, float64 for
         the reference's data file).  ``rows=(r0, r1)`` renders only that pixel-row band ([N, r1-r0, W, 3]);
         ``allreduce_minmax`` is the hook row-tiled multi-GPU rendering uses for the global min/max of modes
         1/2/5 (see ray_marching_amd/distributed.py); ``tile_order`` / ``tile_cost``: rm_render_forward's
-        scheduling hint and per-tile cost output (include/rm_abi.h)."""
-        mode = mode % 8
+        scheduling hint and per-tile cost output (include/rm_abi.h).  ``mode``: one of the reference's eight shaders, or an
+        instance of a class registered with extensions.register_shader ([N, H, W, 3] in the module's dtype; its own
+        parameters receive gradients like the scene's)."""
+        mode, cs = resolve_mode(self.scene, mode, self.precision)
         r0 = self.camera.rows[0]
         if rows is not None and r0:          # a band loop: frame rows -> rows of its own buffers
             if rows[0] < r0 or rows[1] > self.camera.rows[1]:
                 raise ValueError(f"rows {tuple(rows)} outside this loop's band {self.camera.rows}")
             rows = (rows[0] - r0, rows[1] - r0)
-        cs = compiled_for(self.scene)
         training = torch.is_grad_enabled() and (orientations.requires_grad or translations.requires_grad
                                                 or any(p.requires_grad for p in cs.leaves))
         rp, rd = self._io_buffers(training)

@@ -199,6 +199,14 @@ int rm_user_warps(void) {
 #endif
 }
 
+int rm_user_shaders(void) {
+#ifdef RM_USER_SHADER
+  return 1;
+#else
+  return 0;
+#endif
+}
+
 const char* rm_last_error(void) { return g_err; }
 
 int64_t rm_grad_partials_floats(const RmScene* scene, int64_t n) {
@@ -356,7 +364,11 @@ int rm_render_forward(const RmScene* scene, const RmCamera* cam, const RmTetra* 
                       float* park_ws, int64_t park_capacity, void* stream) {
   if (int e = check_render(scene, cam, tetra, orientation, translation, steps, row_begin, row_end)) return e;
   if (!image) return fail(RM_E_BADARG, "rm_render_forward: null image");
+#ifdef RM_USER_SHADER
+  if (mode < 0 || mode > RM_MODE_USER) return fail(RM_E_BADARG, "rm_render_forward: mode %d not in 0..8", mode);
+#else
   if (mode < 0 || mode > 7) return fail(RM_E_BADARG, "rm_render_forward: mode %d not in 0..7", mode);
+#endif
   const bool global = (mode == RM_MODE_DISTANCE || mode == RM_MODE_PROXIMITY || mode == RM_MODE_LAPLACIAN);
   const bool mapped = (mode == RM_MODE_TANGENT || mode == RM_MODE_SPIN);
   if (global && (!minmax || !first_pass))
@@ -591,8 +603,13 @@ int rm_render_backward(const RmScene* scene, const RmCamera* cam, const RmTetra*
   if (int e = check_render(scene, cam, tetra, orientation, translation, steps, row_begin, row_end)) return e;
   if (cam->dtype != RM_DTYPE_F32) return fail(RM_E_BADARG, "rm_render_backward: fp32 camera buffers only");
   const bool mapped = (mode == RM_MODE_TANGENT || mode == RM_MODE_SPIN);
+#ifdef RM_USER_SHADER
+  if (mode < 0 || mode > RM_MODE_USER) return fail(RM_E_BADARG, "rm_render_backward: mode %d not in 0..8", mode);
+  const int kind = (mode == RM_MODE_LAPLACIAN) ? 1 : (mode == RM_MODE_PROXIMITY ? 2 : (mode == RM_MODE_DISTANCE ? 3 : (mode == RM_MODE_USER ? 4 : 0)));
+#else
   if (mode < 0 || mode > 7) return fail(RM_E_BADARG, "rm_render_backward: mode %d not in 0..7", mode);
   const int kind = (mode == RM_MODE_LAPLACIAN) ? 1 : (mode == RM_MODE_PROXIMITY ? 2 : (mode == RM_MODE_DISTANCE ? 3 : 0));
+#endif
   if (mapped && (!cmap || cmap_size <= 0 || cmap_dtype < RM_DTYPE_F32 || cmap_dtype > RM_DTYPE_F64))
     return fail(RM_E_BADARG, "rm_render_backward: mode %d needs the colormap of the forward call", mode);
   if (!p_final || !grad_image || !partials || (steps > 0 && !traj)) return fail(RM_E_BADARG, "rm_render_backward: null buffer");
@@ -610,6 +627,9 @@ int rm_render_backward(const RmScene* scene, const RmCamera* cam, const RmTetra*
   if (int e = kind == 1 ? pick_launch(rm::k_render_bwd<GB, 1>, *scene, true, 128, &L)
             : kind == 2 ? pick_launch(rm::k_render_bwd<GB, 2>, *scene, true, 128, &L)
             : kind == 3 ? pick_launch(rm::k_render_bwd<GB, 3>, *scene, true, 128, &L)
+#ifdef RM_USER_SHADER
+            : kind == 4 ? pick_launch(rm::k_render_bwd<GB, 4>, *scene, true, 128, &L)
+#endif
                         : pick_launch(rm::k_render_bwd<GB, 0>, *scene, true, 128, &L)) return e;
   int64_t wave_tiles;
   {
@@ -645,6 +665,9 @@ int rm_render_backward(const RmScene* scene, const RmCamera* cam, const RmTetra*
   if (kind == 1) rm::k_render_bwd<GB, 1><<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
   else if (kind == 2) rm::k_render_bwd<GB, 2><<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
   else if (kind == 3) rm::k_render_bwd<GB, 3><<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
+#ifdef RM_USER_SHADER
+  else if (kind == 4) rm::k_render_bwd<GB, 4><<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
+#endif
   else rm::k_render_bwd<GB, 0><<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
   if (int e = launched("k_render_bwd")) return e;
   int rows = grid;

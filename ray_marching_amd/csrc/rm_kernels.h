@@ -935,10 +935,38 @@ struct ShadeIn {
   V3 col2;            // pixel_frames[..., 2]
 };
 
+// dL/d(ShadeIn) as the VJP of a user-defined shader fills it in (arrives zeroed; lap and dist have no entry: a user shader
+// does not read them)
+struct ShadeGrad {
+  V3 o, v, p, n, col2;
+  float qw; V3 qv;
+};
+
+// User-defined per-pixel shader (RM_MODE_USER; extensions.register_shader).  The code header of a specialised library is
+// included a third time here, behind ShadeIn / ShadeGrad and still inside namespace rm, for its shader section alone
+// (RM_STATIC_CODE_LEAVES keeps the program section of a header without one out):
+//     #define RM_USER_SHADER 1, RM_USER_SHADER_THETA <offset of theta in the scene block>, RM_USER_SHADER_PARAMS <floats>,
+//     template <bool Fast> RM_DEV rm::V3 NAME_fwd(const rm::ShadeIn& s, const float* theta);
+//     template <bool Fast> RM_DEV void   NAME_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 g, rm::ShadeGrad& gs, float* gtheta);
+// and user_shader_fwd / user_shader_vjp, which forward to them.  Without RM_USER_SHADER (the generic libraries, every
+// library of a scene alone) nothing of it exists.
+#ifdef RM_STATIC_CODE
+#define RM_STATIC_CODE_LEAVES
+#define RM_STATIC_CODE_SHADER
+#include RM_STATIC_CODE
+#undef RM_STATIC_CODE_SHADER
+#undef RM_STATIC_CODE_LEAVES
+#endif
+
 // One pixel of Shader.forward (shader.py:190-263).  Modes 1, 2, 5 return the
 // un-normalised value; rm_shade_finish applies the global min/max.
-RM_DEV Shaded shade_pixel(int mode, const ShadeIn& s, int cmap_size, int degree) {
+// `theta` (RM_MODE_USER only): the user shader's parameter floats, copied out of the staged block by the caller.
+RM_DEV Shaded shade_pixel(int mode, const ShadeIn& s, int cmap_size, int degree, [[maybe_unused]] const float* theta = nullptr) {
   switch (mode) {
+#ifdef RM_USER_SHADER
+    case RM_MODE_USER:          // (theta: the caller's local array, filled with constant indices, so it dissolves into registers)
+      return plain(user_shader_fwd<false>(s, theta));
+#endif
     case RM_MODE_LAMBERTIAN: {  // shader.py:16-20
       float c = t_clamp(-dot_seq(s.v, s.n), 0.0f, 1.0f);
       return plain(mk3(c, c, c));
@@ -1127,7 +1155,17 @@ RM_DEV void finish_tile(const RenderArgs& a, const SceneT& scene, const Tetra& T
     float w = r.ps.w, x = r.ps.qv.x, y = r.ps.qv.y, z = r.ps.qv.z;
     si.col2 = mk3(2.0f * (w * y + x * z), 2.0f * (y * z - w * x), ((w * w - x * x) - y * y) + z * z);
   }
+#ifdef RM_USER_SHADER
+  if (mode == RM_MODE_USER) si.lap = 0.0f;      // (the taps' sum without the centre value is no Laplacian: a user shader reads 0)
+  // theta out of the staged block into a local array, as RM_OP_USER does: constant indices, so it dissolves into the registers
+  // the block lives in
+  float theta[RM_USER_SHADER_PARAMS > 0 ? RM_USER_SHADER_PARAMS : 1] = {};
+#pragma unroll
+  for (int i = 0; i < RM_USER_SHADER_PARAMS; ++i) theta[i] = scene.P[RM_USER_SHADER_THETA + i];
+  const Shaded sh = shade_pixel(mode, si, a.cmap_size, a.degree, theta);
+#else
   const Shaded sh = shade_pixel(mode, si, a.cmap_size, a.degree);
+#endif
   const V3 out = sh.rgb;
   const bool global = (mode == RM_MODE_DISTANCE || mode == RM_MODE_PROXIMITY || mode == RM_MODE_LAPLACIAN);
   if (r.live) {
@@ -1928,6 +1966,10 @@ struct DeferToList {
 //   kKind 3, mode 1: log(clamp(|origin - p|, 1e-2, inf)) -- no scene evaluation, but three more live registers;
 //   kKind 2, mode 2: log(clamp(scene(p), 1e-2, inf)) -- one scene VJP at the surface point;
 //   kKind 1, mode 5: the five-tap Laplacian -- the four taps plus the centre.
+//   kKind 4, mode 8 (RM_USER_SHADER libraries only): the user-defined shader.  Its VJP hands back dL/d(o, v, p, n, col2, q) and
+//   dL/dtheta; n goes through normals_backward, p joins the lambda that comes out of it, v starts the direction gradient, o
+//   takes kind 3's road to grad_pos, col2 is chained to the quaternion like the vignette's, theta goes to the accumulators
+//   behind the scene's own (RM_USER_SHADER_THETA).  The reverse march always runs.
 // Separate instantiations: kinds 1 and 2 add an inlined scene VJP, and kind 3 inside kind 0 cost the training step's
 // backward kernel 43 % (116 -> 166 us: registers across the reverse march) -- the per-pixel modes carry none of it.
 template <class Cfg, int kKind = 0>
@@ -1972,7 +2014,31 @@ __global__ void __launch_bounds__(256) RM_BWD_OCC k_render_bwd(RenderArgs a) {
     V3 gv = mk3(0.0f, 0.0f, 0.0f);
     float gq0 = 0.0f, gq1 = 0.0f, gq2 = 0.0f, gq3 = 0.0f;     // direct dependence of the shader on the pose quaternion
     [[maybe_unused]] V3 gp_direct = mk3(0.0f, 0.0f, 0.0f);   // kind 3: direct dependence of the shader on the origin (- on the surface point)
-    if constexpr (kKind == 3) {
+    [[maybe_unused]] V3 gp_surface = mk3(0.0f, 0.0f, 0.0f);  // kind 4: direct dependence of the user shader on the surface point
+    if constexpr (kKind == 4) {
+#ifdef RM_USER_SHADER
+      // every lane gets here (a lane without a ray runs on ray 0 with a zero upstream): the accumulator rows sum over the wave
+      ShadeIn si;
+      si.o = qrot(load3(static_cast<const float*>(a.cam.ray_positions), gi), ps.w, ps.qv) + ps.t;
+      si.v = v; si.p = p; si.n = n; si.lap = 0.0f; si.dist = 0.0f; si.qw = ps.w; si.qv = ps.qv;
+      const float w = ps.w, x = ps.qv.x, y = ps.qv.y, z = ps.qv.z;
+      si.col2 = mk3(2.0f * (w * y + x * z), 2.0f * (y * z - w * x), ((w * w - x * x) - y * y) + z * z);
+      float theta[RM_USER_SHADER_PARAMS > 0 ? RM_USER_SHADER_PARAMS : 1] = {}, gtheta[RM_USER_SHADER_PARAMS > 0 ? RM_USER_SHADER_PARAMS : 1] = {};
+#pragma unroll
+      for (int i = 0; i < RM_USER_SHADER_PARAMS; ++i) theta[i] = scene.P[RM_USER_SHADER_THETA + i];
+      const V3 z3 = mk3(0.0f, 0.0f, 0.0f);
+      ShadeGrad gs{z3, z3, z3, z3, z3, 0.0f, z3};
+      user_shader_vjp<(RM_FAST_VJP != 0)>(si, theta, gi3, gs, gtheta);
+#pragma unroll
+      for (int i = 0; i < RM_USER_SHADER_PARAMS; ++i) scene.st->add(scene.acc0 + RM_USER_SHADER_THETA + i, live ? gtheta[i] : 0.0f);
+      gn = gs.n; gv = gs.v; gp_direct = gs.o; gp_surface = gs.p;
+      const V3 gc = gs.col2;      // col2(q) = third column of QuaternionToSO3: the vignette's four lines, plus the direct terms
+      gq0 = 2.0f * ((gc.x * y - gc.y * x) + gc.z * w) + gs.qw;
+      gq1 = 2.0f * ((gc.x * z - gc.y * w) - gc.z * x) + gs.qv.x;
+      gq2 = 2.0f * ((gc.x * w + gc.y * z) - gc.z * y) + gs.qv.y;
+      gq3 = 2.0f * ((gc.x * x + gc.y * y) + gc.z * z) + gs.qv.z;
+#endif
+    } else if constexpr (kKind == 3) {
       // norm(origin - p).clamp(1e-2, inf).log(): grad / clamped, masked by the clamp, along (origin - p) / norm
       const V3 o = qrot(load3(static_cast<const float*>(a.cam.ray_positions), gi), ps.w, ps.qv) + ps.t;
       const V3 d = o - p;
@@ -2071,6 +2137,7 @@ __global__ void __launch_bounds__(256) RM_BWD_OCC k_render_bwd(RenderArgs a) {
         lam = neg(gp_direct);
       } else {
         lam = normals_backward(scene, T, p, u, gn, kKind == 1 ? gi3.x : 0.0f, kKind == 1);
+        if constexpr (kKind == 4) lam = lam + gp_surface;
       }
       RM_STAMP(stamps, 1);
       int ne = a.nexec ? a.nexec[li] : a.steps;
@@ -2081,7 +2148,7 @@ __global__ void __launch_bounds__(256) RM_BWD_OCC k_render_bwd(RenderArgs a) {
       RM_STAMP(stamps, 6);
     }
     if (a.tile_cost && (threadIdx.x & 63) == 0) a.tile_cost[tc.tile] = walked;
-    if constexpr (kKind == 3) {
+    if constexpr (kKind == 3 || kKind == 4) {
       if (live && a.grad_pos) store3(a.grad_pos, li, deferred ? gp_direct : lam + gp_direct);   // (deferred: k_bwd_hard_a adds its part)
     } else {
       if (live && !deferred && a.grad_pos) store3(a.grad_pos, li, lam);
@@ -2235,7 +2302,11 @@ __global__ void k_bwd_hard_a(RenderArgs a) {
     gv = gv + sumf * lam;
   }
   // (distance shader: k_render_bwd left the shader's direct dependence on the origin there for the deferred rays)
+#ifdef RM_USER_SHADER     // (... and so did a user shader)
+  if (valid && a.grad_pos) store3(a.grad_pos, li, (a.mode == RM_MODE_DISTANCE || a.mode == RM_MODE_USER) ? lam + load3(a.grad_pos, li) : lam);
+#else
   if (valid && a.grad_pos) store3(a.grad_pos, li, a.mode == RM_MODE_DISTANCE ? lam + load3(a.grad_pos, li) : lam);
+#endif
   if (valid && a.grad_dirs) store3(a.grad_dirs, li, gv);
 }
 

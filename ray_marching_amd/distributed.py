@@ -30,8 +30,10 @@ GREY_MODES = (0, 1, 2, 3, 5)
 
 
 def tile_payload(tile: torch.Tensor, mode: int) -> torch.Tensor:
-    """What a rank sends for its tile [N, rows, W, 3]: channel 0 alone for the grey shaders."""
-    return tile[..., :1].contiguous() if mode % 8 in GREY_MODES else tile.contiguous()
+    """What a rank sends for its tile [N, rows, W, 3]: channel 0 alone for the grey shaders (a user shader,
+    extensions.register_shader, is per pixel and coloured: all three)."""
+    grey = not isinstance(mode, torch.nn.Module) and mode % 8 in GREY_MODES
+    return tile[..., :1].contiguous() if grey else tile.contiguous()
 
 
 def expand_payload(frame: torch.Tensor) -> torch.Tensor:
@@ -161,7 +163,7 @@ class RowTileRenderer:
             # surplus rank: nothing to render, but it takes part in every exchange (incl. the min/max all-reduce);
             # everything it needs is known BEFORE the first collective, so it cannot fail while the others wait
             tile = self._empty_tile(like)
-            if mode % 8 in (1, 2, 5):
+            if not isinstance(mode, torch.nn.Module) and mode % 8 in (1, 2, 5):
                 lohi = torch.tensor([float("inf"), float("-inf")], device=tile.device)
                 self._allreduce_minmax(lohi)
         tile = tile_payload(tile, mode)

@@ -59,7 +59,21 @@ class keeps ``warp(points) -> points``, ``out(values, points) -> values`` where 
 is ``out(child(warp(p)), p)``.  The field must stay a conservative distance (Lipschitz <= 1): that is the user's to see to, as
 for leaves.  A warp signs no bound: no cull test covers a subtree that contains one (culling inside its child is untouched).
 
-Scenes that contain such a leaf, combinator or warp run only through their per-scene specialised library (specialize.py), into which
+User-defined *shaders* are the fourth kind, and the only one that is no scene node: ``register_shader`` teaches the frame kernels a
+per-pixel shader, passed to ``RenderLoop.forward`` (``capture``, ``training_step``, ``display_frame``) as ``mode``,
+
+    template <bool Fast> RM_DEV rm::V3 NAME_fwd(const rm::ShadeIn& s, const float* theta);
+    template <bool Fast> RM_DEV void   NAME_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 g, rm::ShadeGrad& gs, float* gtheta);
+
+``s`` holds the pixel's ray origin ``o``, direction ``v``, surface point ``p``, unit normal ``n``, the pose quaternion ``qw, qv`` and
+``col2``, the third column of the camera rotation (``lap`` and ``dist`` read as 0); ``theta`` is the shader's own parameters,
+flattened in ``named_parameters()`` order; ``g`` is dL/d(rgb); ``gs`` arrives zeroed, the VJP adds dL/d(input) into it and writes
+``gtheta[i]``.  The class keeps its PyTorch ``forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords,
+surface_normals) -> [..., 3]`` untouched: called directly, a shader is the user's PyTorch code on whatever device its inputs
+are on.  A (scene, shader) pair is compiled into one library (compiler.compiled_with_shader); the shader's parameters follow the
+scene's in the parameter block and receive their gradients through the same accumulators.
+
+Scenes that contain such a leaf, combinator or warp, and frames shaded by such a shader, run only through their per-scene specialised library (specialize.py), into which
 the source is compiled; the LDS interpreter has no handler for them and ``CompiledScene.lib()`` says so instead of
 rendering a wrong picture.
 """
@@ -73,7 +87,7 @@ import torch
 import torch.nn as nn
 
 __all__ = ["register_leaf", "leaf_spec", "check_bound", "UserLeaf", "register_combinator", "combinator_spec", "UserCombinator",
-           "register_warp", "warp_spec", "UserWarp"]
+           "register_warp", "warp_spec", "UserWarp", "register_shader", "shader_spec", "UserShader"]
 
 
 @dataclass(frozen=True)
@@ -110,9 +124,19 @@ class UserWarp:
     has_out: bool       # the source brings NAME_out_fwd / NAME_out_vjp (and the class an ``out`` method)
 
 
+@dataclass(frozen=True)
+class UserShader:
+    cls: type
+    name: str           # NAME of NAME_fwd / NAME_vjp
+    params: tuple       # attribute names of the shader's nn.Parameters, named_parameters() order
+    hip: str
+    sha1: str
+
+
 _registry: dict[type, UserLeaf] = {}
 _combinators: dict[type, UserCombinator] = {}
 _warps: dict[type, UserWarp] = {}
+_shaders: dict[type, UserShader] = {}
 
 _DEF = r"\b([A-Za-z_]\w*)_%s\s*\("
 
@@ -164,6 +188,18 @@ def _warp_identifier(hip: str):
     if re.search(r"\basm\b|__asm", text):
         raise ValueError("a user warp must not contain inline assembly (INTEGRATION.md: warp contract)")
     return name, out_fwd
+
+
+def _shader_identifier(hip: str) -> str:
+    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
+    fwd, vjp = (set(re.findall(r"RM_DEV\s+%s\s+" % ret + _DEF % kind, text)) for ret, kind in ((r"(?:rm::)?V3", "fwd"), ("void", "vjp")))
+    if len(fwd) != 1 or fwd != vjp:
+        raise ValueError("hip must define exactly two device functions, `template <bool Fast> RM_DEV rm::V3 NAME_fwd(const rm::ShadeIn& s, "
+                         "const float* theta)` and `template <bool Fast> RM_DEV void NAME_vjp(const rm::ShadeIn& s, const float* theta, "
+                         f"rm::V3 g, rm::ShadeGrad& gs, float* gtheta)`, with one NAME (found fwd: {sorted(fwd)}, vjp: {sorted(vjp)})")
+    if re.search(r"\basm\b|__asm", text):
+        raise ValueError("a user shader must not contain inline assembly (INTEGRATION.md: shader contract)")
+    return fwd.pop()
 
 
 def _has_bound(hip: str, name: str) -> bool:
@@ -238,13 +274,15 @@ def register_leaf(cls, *, params, hip: str, cost: int):
         if (old.sha1, old.params, old.cost) != (spec.sha1, spec.params, spec.cost):
             raise ValueError(f"register_leaf: {cls.__name__} is already registered with different source, parameters or cost")
         return cls
-    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()):
+    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()) + list(_shaders.values()):
         if other.name == spec.name:          # (the user types of one scene are compiled into one translation unit)
             raise ValueError(f"register_leaf: the identifier {spec.name!r} is already used by {other.cls.__name__}")
     if _registered_class(cls, _combinators) is not None:
         raise TypeError(f"register_leaf: {cls.__name__} is already registered as a combinator")
     if _registered_class(cls, _warps) is not None:
         raise TypeError(f"register_leaf: {cls.__name__} is already registered as a warp")
+    if _registered_class(cls, _shaders) is not None:
+        raise TypeError(f"register_leaf: {cls.__name__} is already registered as a shader")
     cls._rm_torch_forward = _torch_forward(cls)
     cls.forward = _device_forward
     _registry[cls] = spec
@@ -297,7 +335,9 @@ def register_combinator(cls, *, params=(), hip: str, cost: int = 4, children: st
         raise TypeError(f"register_combinator: {cls.__name__} is already registered as a leaf")
     if _registered_class(cls, _warps) is not None:
         raise TypeError(f"register_combinator: {cls.__name__} is already registered as a warp")
-    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()):
+    if _registered_class(cls, _shaders) is not None:
+        raise TypeError(f"register_combinator: {cls.__name__} is already registered as a shader")
+    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()) + list(_shaders.values()):
         if other.name == spec.name:
             raise ValueError(f"register_combinator: the identifier {spec.name!r} is already used by {other.cls.__name__}")
     cls._rm_torch_forward = _torch_forward(cls)
@@ -346,6 +386,8 @@ def register_warp(cls, *, params=(), hip: str, cost: int = 10, child: str = "sdf
         raise TypeError(f"register_warp: {cls.__name__} is already registered as a leaf")
     if _registered_class(cls, _combinators) is not None:
         raise TypeError(f"register_warp: {cls.__name__} is already registered as a combinator")
+    if _registered_class(cls, _shaders) is not None:
+        raise TypeError(f"register_warp: {cls.__name__} is already registered as a shader")
     if not callable(getattr(cls, "warp", None)):
         raise TypeError(f"register_warp: {cls.__name__} has no warp(points [..., 3]) -> [..., 3] method")
     if not isinstance(child, str) or not child:
@@ -367,7 +409,7 @@ def register_warp(cls, *, params=(), hip: str, cost: int = 10, child: str = "sdf
             raise ValueError(f"register_warp: {cls.__name__} is already registered with different source, parameters, cost or "
                              "child attribute")
         return cls
-    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()):
+    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()) + list(_shaders.values()):
         if other.name == spec.name:
             raise ValueError(f"register_warp: the identifier {spec.name!r} is already used by {other.cls.__name__}")
     cls._rm_torch_forward = _torch_forward(cls)
@@ -388,6 +430,61 @@ def warp_child(node, spec: UserWarp):
     if not isinstance(kid, nn.Module):
         raise ValueError(f"{type(node).__name__}: the child attribute {spec.child!r} is missing or not an SDF module")
     return kid
+
+
+def register_shader(cls, *, params=(), hip: str):
+    """Make instances of ``cls`` (an ``nn.Module`` subclass) usable as the ``mode`` of ``RenderLoop.forward``: a per-pixel shader
+    that runs fused at the end of the frame kernels and in the fused backward.
+
+    params: names of ALL its ``nn.Parameter`` attributes in ``named_parameters()`` order (may be empty): ``theta``.
+    hip:    source of NAME_fwd / NAME_vjp (module docstring).
+
+    ``cls`` has ``forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals) -> [..., 3]``,
+    the first six arguments of the reference's ``Shader.forward`` (``camera_orientation`` [N,4], ``pixel_frames`` [N,3,3]); it is
+    the CPU statement of the shader and is NOT replaced.  Registering a class again with the same source is a no-op; with other
+    source or parameters it is an error.  Identifiers are unique across leaves, combinators, warps and shaders."""
+    if not (isinstance(cls, type) and issubclass(cls, nn.Module)):
+        raise TypeError(f"register_shader: {cls!r} is not an nn.Module subclass")
+    if getattr(cls, "_rm_kind", None) is not None:
+        raise TypeError(f"register_shader: {cls.__name__} is already a ray_marching_amd node")
+    for registry, what in ((_registry, "leaf"), (_combinators, "combinator"), (_warps, "warp")):
+        if _registered_class(cls, registry) is not None:
+            raise TypeError(f"register_shader: {cls.__name__} is already registered as a {what}")
+    if cls.forward is nn.Module.forward:
+        raise TypeError(f"register_shader: {cls.__name__} has no forward(px_coords, camera_orientation, pixel_frames, ray_directions, "
+                        "surface_coords, surface_normals)")
+    params = tuple(params)
+    if not all(isinstance(p, str) for p in params) or len(set(params)) != len(params):
+        raise ValueError("register_shader: params must be distinct attribute names")
+    name = _shader_identifier(hip)
+    spec = UserShader(cls, name, params, hip, hashlib.sha1(hip.encode()).hexdigest())
+    old = _shaders.get(cls)
+    if old is not None:
+        if (old.sha1, old.params) != (spec.sha1, spec.params):
+            raise ValueError(f"register_shader: {cls.__name__} is already registered with different source or parameters")
+        return cls
+    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()) + list(_shaders.values()):
+        if other.name == spec.name:          # (a scene's user types and the shader are compiled into one translation unit)
+            raise ValueError(f"register_shader: the identifier {spec.name!r} is already used by {other.cls.__name__}")
+    _shaders[cls] = spec
+    return cls
+
+
+def shader_spec(node):
+    """The shader registration of this module's class (or of the registered class it derives from), or None."""
+    c = _registered_class(type(node), _shaders)
+    return None if c is None else _shaders[c]
+
+
+def shader_parameters(shader, spec: UserShader):
+    """The shader's nn.Parameters in theta order: the registered names, which must be all of its parameters in
+    ``named_parameters()`` order."""
+    params = leaf_parameters(shader, spec)
+    own = [p for _, p in shader.named_parameters()]
+    if len(own) != len(params) or any(a is not b for a, b in zip(own, params)):
+        raise ValueError(f"{type(shader).__name__}: the registered params {spec.params} are not all of the shader's parameters in "
+                         f"named_parameters() order ({[n for n, _ in shader.named_parameters()]})")
+    return params
 
 
 def leaf_parameters(node, spec):

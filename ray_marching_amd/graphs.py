@@ -69,14 +69,17 @@ class CapturedTrainingStep:
     The scene parameters are read in place by the kernels (CompiledScene.param_table), so optimiser steps and in-place
     edits between calls need nothing; `.grad` of every parameter is a static buffer the replays overwrite (set them to
     None / rebuild the step after changing which parameters require grad).  The pose may change from call to call (it
-    is copied into static buffers); the frame size, shader mode, step count and the loss function are part of the graph.
+    is copied into static buffers); the frame size, shader mode (or user shader, whose parameters are leaves like the scene's), step
+    count and the loss function are part of the graph.
     The first call runs two warm-up iterations at its pose before capturing (real iterations: with ``optimizer=`` they
     take optimiser steps, as torch's own whole-network capture recipe does)."""
 
-    def __init__(self, loop, loss_fn, mode: int = 0, degree: int = 1, marching_steps: int = 32, optimizer=None,
+    def __init__(self, loop, loss_fn, mode=0, degree: int = 1, marching_steps: int = 32, optimizer=None,
                  pose_requires_grad: bool = False):
         self.loop, self.loss_fn, self.optimizer = loop, loss_fn, optimizer
-        self.mode, self.degree, self.steps = int(mode), int(degree), int(marching_steps)
+        # (an instance of a registered shader class stays what it is: RenderLoop.forward resolves it)
+        self.mode = mode if isinstance(mode, torch.nn.Module) else int(mode)
+        self.degree, self.steps = int(degree), int(marching_steps)
         self.pose_requires_grad = pose_requires_grad
         self.graph = None
 
@@ -85,6 +88,8 @@ class CapturedTrainingStep:
         self.q = orientations.detach().clone().requires_grad_(self.pose_requires_grad)
         self.t = translations.detach().clone().requires_grad_(self.pose_requires_grad)
         self.params = [p for p in loop.scene.parameters() if p.requires_grad]
+        if isinstance(self.mode, torch.nn.Module):       # a user shader's own parameters are trained with the scene's
+            self.params += [p for p in self.mode.parameters() if p.requires_grad]
         leaves = self.params + ([self.q, self.t] if self.pose_requires_grad else [])
 
         def step():

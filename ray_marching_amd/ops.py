@@ -385,7 +385,7 @@ workspaces = _Workspaces()
 # fused frame
 # --------------------------------------------------------------------------
 _GLOBAL_MODES = (1, 2, 5)
-_FUSED_VJP_MODES = {0, 1, 2, 3, 4, 5, 6, 7}   # shader modes rm_render_backward differentiates through
+_FUSED_VJP_MODES = {0, 1, 2, 3, 4, 5, 6, 7, _abi.MODE_USER}   # shader modes rm_render_backward differentiates through
 
 
 def minmax_normalisation_vjp(grad_image: torch.Tensor, logd: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
@@ -606,9 +606,9 @@ class Render(torch.autograd.Function):
             need_pose = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
             gpos = torch.empty_like(p_final) if need_pose else None
             gdirs = torch.empty_like(p_final) if ctx.needs_input_grad[1] else None
-            # modes 3, 6, 7 use the pose quaternion in the shader itself: per-ray dL/dq, summed per camera below
+            # modes 3, 6, 7 (and a user shader) use the pose quaternion in the shader itself: per-ray dL/dq, summed per camera below
             gqdir = torch.empty(p_final.shape[:-1] + (4,), dtype=torch.float32, device=dev) \
-                if (ctx.needs_input_grad[1] and ctx.mode in (3, 6, 7)) else None
+                if (ctx.needs_input_grad[1] and ctx.mode in (3, 6, 7, _abi.MODE_USER)) else None
             cmap = ctx.cmap if ctx.mode in (6, 7) else None
             # deferred-ray workspace: room for one ray in eight (config 4 defers 2 %; the rest is walked in place)
             hard_cap = 0 if (bwd_hard_capacity == 0 or ctx.steps == 0) else \

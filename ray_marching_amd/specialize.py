@@ -23,7 +23,7 @@ Policy (env RM_SPECIALIZE):
   "off"      always interpret.
 
 Scenes with user-defined leaves, combinators or warps (extensions.register_leaf / register_combinator / register_warp; their
-HIP source is compiled into the library) have no
+HIP source is compiled into the library) and (scene, shader) programs (extensions.register_shader) have no
 interpreter to start on: "auto" and "jit" both build a missing library synchronously on first use, "prebuilt" and
 "off" raise RmError (load_user).
 """
@@ -163,11 +163,27 @@ def _warp_section(cs: CompiledScene) -> str:
         "  switch (type) {\n" + cases_ov + "    default: break;\n  }\n}\n")
 
 
+def _shader_section(cs: CompiledScene) -> str:
+    """The user shader's source and the two functions the frame kernels call, for the header's inclusion from csrc/rm_kernels.h
+    (behind rm::ShadeIn / rm::ShadeGrad, inside namespace rm)."""
+    name, floats, sha = cs.user_shader
+    return (
+        "#define RM_USER_SHADER 1\n"
+        f"#define RM_USER_SHADER_THETA {cs.shader_offset}\n"
+        f"#define RM_USER_SHADER_PARAMS {floats}\n"
+        f"// user shader: {name}, {floats} parameter floats, sha1 {sha}\n{cs.user_shader_source.strip()}\n"
+        "template <bool Fast> RM_DEV V3 user_shader_fwd(const ShadeIn& s, const float* theta) {\n"
+        f"  return {name}_fwd<Fast>(s, theta);\n}}\n"
+        "template <bool Fast> RM_DEV void user_shader_vjp(const ShadeIn& s, const float* theta, V3 g, ShadeGrad& gs, float* gtheta) {\n"
+        f"  {name}_vjp<Fast>(s, theta, g, gs, gtheta);\n}}\n")
+
+
 def user_names(cs: CompiledScene):
     """(names, what) of the user types of a scene, for messages: leaf-only scenes read as they always did."""
     kinds = [("leaves", [name for name, _, _ in cs.user_leaves]),
              ("combinators", list(dict.fromkeys(name for name, _, _, _ in cs.user_combinators))),
-             ("warps", [name for name, _, _, _ in cs.user_warps])]
+             ("warps", [name for name, _, _, _ in cs.user_warps]),
+             ("shaders", [name for name in cs.user_shader[:1]])]
     kinds = [(what, names) for what, names in kinds if names]
     if len(kinds) <= 1:
         what, names = kinds[0] if kinds else ("leaves", [])
@@ -184,14 +200,17 @@ def code_header(cs: CompiledScene) -> str:
         f"                       stack_floats = {cs.stack_floats}, n_slots = {cs.n_slots}, n_grad_derived = {cs.n_grad_derived};\n"
         f"  static constexpr rm::Ins code[{cs.n_instr}] = {{{rows}}};\n"
         "};\n")
-    # included twice: by csrc/rm_device.h in front of the handlers (RM_STATIC_CODE_LEAVES: the user leaves only), then by
-    # csrc/rm_abi.hip for the program
+    # included three times: by csrc/rm_device.h in front of the handlers (RM_STATIC_CODE_LEAVES: the user leaves, combinators and
+    # warps only), by csrc/rm_kernels.h behind ShadeIn / ShadeGrad (RM_STATIC_CODE_LEAVES and RM_STATIC_CODE_SHADER: the user
+    # shader only), then by csrc/rm_abi.hip for the program
     head = "// generated by ray_marching_amd/specialize.py -- scene program as a compile-time constant\n"
-    if not cs.user_leaves and not cs.user_combinators and not cs.user_warps:
+    if not cs.user_leaves and not cs.user_combinators and not cs.user_warps and not cs.user_shader:
         return head + "#ifndef RM_STATIC_CODE_LEAVES\n" + program + "#endif\n"
     user = ((_leaf_section(cs) if cs.user_leaves else "") + (_combinator_section(cs) if cs.user_combinators else "")
             + (_warp_section(cs) if cs.user_warps else ""))
-    return head + "#ifdef RM_STATIC_CODE_LEAVES\n" + user + "#else\n" + program + "#endif\n"
+    shader = _shader_section(cs) if cs.user_shader else ""
+    return (head + "#if defined(RM_STATIC_CODE_SHADER)\n" + shader + "#elif defined(RM_STATIC_CODE_LEAVES)\n" + user
+            + "#else\n" + program + "#endif\n")
 
 
 def lib_path(cs: CompiledScene, precision: str = "exact") -> str:
@@ -242,7 +261,7 @@ def build(cs: CompiledScene, force: bool = False, precision: str = "exact") -> s
     if not static_backward(cs):
         cmd.append("-DRM_NO_BACKWARD")
     cmd += [os.path.join(CSRC, "rm_abi.hip"), "-o", tmp]
-    if not cs.user_leaves and not cs.user_combinators and not cs.user_warps:
+    if not cs.user_leaves and not cs.user_combinators and not cs.user_warps and not cs.user_shader:
         subprocess.run(cmd, check=True, cwd=CSRC)
     else:
         # user source goes through the compiler here: its diagnostics belong in the exception, and the frame kernel's
@@ -305,7 +324,7 @@ def load(cs: CompiledScene, precision: str = "exact"):
 
 
 def load_user(cs: CompiledScene, precision: str = "exact"):
-    """The library of a scene with user-defined leaves: never None.  "auto" and "jit" build a missing library now, on
+    """The library of a scene with user-defined leaves (combinators, warps, or a user shader): never None.  "auto" and "jit" build a missing library now, on
     first use (the interpreter cannot bridge the wait); "prebuilt" and "off" raise, naming it."""
     policy = os.environ.get("RM_SPECIALIZE", "auto")
     names, what = user_names(cs)
