@@ -83,14 +83,18 @@ def _cost(node) -> int:
 
 def _boundable(node) -> bool:
     """Can the kernels derive a bounding sphere for this subtree (csrc/rm_device.h: subtree_bound)?
-    Everything except an SDFPlane, a user-defined leaf registered without a NAME_bound, a user-defined combinator or a
-    user-defined warp (which sign no bound) somewhere inside; whether the bound is finite is decided on the device from the live
-    parameter values."""
+    Everything except an SDFPlane, a user-defined leaf or warp registered without a NAME_bound, or a user-defined combinator
+    (which signs no bound) somewhere inside.  A warp's NAME_bound maps its child's bound, so a bounded warp is boundable exactly
+    when its child is; whether the bound is finite is decided on the device from the live parameter values."""
     kind = getattr(node, "_rm_kind", None)
     if kind in ("sphere", "box", "line", "disk", "torus"):
         return True
     if kind is None and _user_leaf(node) is not None:
         return _user_leaf(node).bounded
+    if kind is None and _user_warp(node) is not None:
+        from .extensions import warp_child
+        spec = _user_warp(node)
+        return spec.bounded and _boundable(warp_child(node, spec))
     if kind in ("affine", "rounding", "onion"):
         return _boundable(node.sdf)
     if kind in ("union", "smooth_union"):
@@ -117,6 +121,7 @@ class CompiledScene:
     user_combinator_sources: tuple = () # the HIP source of every combinator CLASS among them (one text per identifier)
     user_warps: tuple = ()              # (identifier, parameter floats, has an `out`, sha1) per user warp type, in aux0 order
     user_warp_sources: tuple = ()       # their HIP source texts
+    user_warp_bounded: tuple = ()       # ... and whether each source brings a NAME_bound (the node's bound from its child's)
     user_shader: tuple = ()             # (identifier, parameter floats, sha1) of the user shader of a (scene, shader) program, else ()
     user_shader_source: str = ""        # its HIP source text
     shader_offset: int = 0              # where its theta starts in the block (= the scene's own n_params)
@@ -545,6 +550,7 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
                          user_sources=tuple(u.hip for u in em.user_types), user_bounded=tuple(u.bounded for u in em.user_types),
                          user_combinators=user_combinators, user_combinator_sources=comb_sources,
                          user_warps=user_warps, user_warp_sources=tuple(u.hip for u in em.warp_types),
+                         user_warp_bounded=tuple(u.bounded for u in em.warp_types),
                          user_shader=user_shader, user_shader_source=shader_source, shader_offset=shader_offset)
 
 

@@ -280,7 +280,9 @@ class SDFMirror(_Warp):
 class SDFRepeat(_Warp):
     """The child repeated without end on the grid of cell size ``period`` (> 0 on every axis): ``sdf(p - period * round(p /
     period))``.  A distance as long as the child stays inside its cell, |x_i| <= period_i / 2, and is symmetric enough that the
-    neighbouring cell's copy is never nearer.  ``round`` is half-to-even and has a zero gradient, as in autograd."""
+    neighbouring cell's copy is never nearer.  ``round`` is half-to-even and has a zero gradient, as in autograd.
+    It has no bounded twin: the copies fill all of space, so no sphere holds the surface and every point is within half a cell
+    diagonal of a copy -- ``node(p) >= slope |p - c| - R`` fails far from any centre whatever R is."""
 
     def __init__(self, sdf, period) -> None:
         super().__init__(sdf)
@@ -376,22 +378,79 @@ register_warp(SDFRepeat, params=("period",), hip=_REPEAT_HIP, cost=45)
 register_warp(SDFElongate, params=("halfsides",), hip=_ELONGATE_HIP, cost=12)
 
 
-def make_warped_scene():
+class SDFBoundedScale(SDFScale):
+    """SDFScale with its bound signed (extensions: a warp's NAME_bound maps its child's bound), so that cull tests cover it where
+    its child is boundable: the same PyTorch methods, the same HIP op stream under an identifier of its own."""
+
+
+class SDFBoundedMirror(SDFMirror):
+    """SDFMirror with its bound signed: one sphere, centred on the mirror plane, around the child's sphere and its image."""
+
+
+class SDFBoundedElongate(SDFElongate):
+    """SDFElongate with its bound signed: the child's sphere, wider by the length of ``halfsides``."""
+
+
+# node(p) = s child(p / s) >= s (slope |p / s - c| - R) = slope |p - s c| - s R for s > 0, and the same from above: the child's
+# sphere scaled about the origin, slopes unchanged.  s <= 0 (or NaN) is no scale: no bound.
+_BSCALE_HIP = _SCALE_HIP.replace("sdf_scale_", "sdf_bscale_") + r"""
+RM_DEV void sdf_bscale_bound(const float* theta, rm::LeafBound& b) {
+  const float s = theta[0];
+  if (s > 0.0f) { b.c = mk3(s * b.c.x, s * b.c.y, s * b.c.z); b.R = s * b.R; b.Ru = s * b.Ru; }
+  else b.R = b.Ru = __builtin_inff();
+}
+"""
+
+# node(p) = child(q), q = (|p.x - o|, p.y, p.z).  With c0 = (0, c.y, c.z):  |q - c0| = |p - (o, c.y, c.z)| and | |q - c| - |q - c0| |
+# <= |c.x|, so  child(q) >= slope (|p - c'| - |c.x|) - R >= slope |p - c'| - (R + |c.x|)  (slope <= 1)  and  child(q) <= uslope |p - c'|
+# + (Ru + uslope |c.x|)  around c' = (o, c.y, c.z).
+_BMIRROR_HIP = _MIRROR_HIP.replace("sdf_mirror_", "sdf_bmirror_") + r"""
+RM_DEV void sdf_bmirror_bound(const float* theta, rm::LeafBound& b) {
+  const float ax = fabsf(b.c.x);
+  b.c.x = theta[0];
+  b.R = (theta[0] == theta[0]) ? b.R + ax : __builtin_inff();          // (a NaN plane: no bound, rather than a NaN centre)
+  b.Ru = (theta[0] == theta[0]) ? b.Ru + b.uslope * ax : __builtin_inff();
+}
+"""
+
+# q = p - clamp(p, -h, h) moves a point by at most |h| (every h_i >= 0), so | |q - c| - |p - c| | <= |h|:  child(q) >= slope |p - c|
+# - (R + |h|)  and  child(q) <= uslope |p - c| + (Ru + uslope |h|).  |h| is rounded up like the capsule's half length.  A negative
+# half-side turns the clamp inside out (the map moves points by more): no bound.
+_BELONGATE_HIP = _ELONGATE_HIP.replace("sdf_elongate_", "sdf_belongate_") + r"""
+RM_DEV void sdf_belongate_bound(const float* theta, rm::LeafBound& b) {
+  const float hx = theta[0], hy = theta[1], hz = theta[2];
+  if (hx >= 0.0f && hy >= 0.0f && hz >= 0.0f) {
+    const float h = sqrtf(hx * hx + hy * hy + hz * hz) * 1.00001f;
+    b.R = b.R + h;
+    b.Ru = b.Ru + b.uslope * h;
+  } else b.R = b.Ru = __builtin_inff();
+}
+"""
+
+register_warp(SDFBoundedScale, params=("scale",), hip=_BSCALE_HIP, cost=36)
+register_warp(SDFBoundedMirror, params=("origin",), hip=_BMIRROR_HIP, cost=3)
+register_warp(SDFBoundedElongate, params=("halfsides",), hip=_BELONGATE_HIP, cost=12)
+
+
+def make_warped_scene(bounded: bool = False):
     """The room of make_test_scene2() around an arrangement that uses all four operators: a scaled torus and an elongated
     sphere, each placed by an affine node, in a union that is mirrored in the plane x = 0 and lifted by another affine node;
     and a grid of small spheres (SDFRepeat) cut to a slab by an SDFIntersection with a box.  The scene whose specialised
-    library build() compiles, so the shipped operators render on a box without a compiler."""
+    library build() compiles, so the shipped operators render on a box without a compiler.
+    ``bounded``: scale, elongation and mirror are the SDFBounded* classes, so the mirrored pair gets a cull test, and so does
+    the scaled torus inside it."""
     from .scene.primitives import SDFBox, SDFSphere, SDFTorus
     from .scene.scene_registry import make_room
     from .scene.transformations import SDFAffineTransformation as A, SDFUnion
+    scale, mirror, elongate = (SDFBoundedScale, SDFBoundedMirror, SDFBoundedElongate) if bounded else (SDFScale, SDFMirror, SDFElongate)
     ident = [1.0, 0.0, 0.0, 0.0]
     pair = SDFUnion([
-        A(SDFScale(SDFTorus(radius1=0.5, radius2=0.12), scale=0.7), orientation=[0.9014, 0.25, 0.25, 0.25], translation=[0.9, 0.4, 0.2]),
-        A(SDFElongate(SDFSphere(radius=0.2), halfsides=(0.05, 0.3, 0.1)), orientation=ident, translation=[0.5, -0.5, -0.3]),
+        A(scale(SDFTorus(radius1=0.5, radius2=0.12), scale=0.7), orientation=[0.9014, 0.25, 0.25, 0.25], translation=[0.9, 0.4, 0.2]),
+        A(elongate(SDFSphere(radius=0.2), halfsides=(0.05, 0.3, 0.1)), orientation=ident, translation=[0.5, -0.5, -0.3]),
     ])
     return SDFUnion([
         make_room(),
-        A(SDFMirror(pair, origin=0.0), orientation=ident, translation=[0.0, 0.2, 0.0]),
+        A(mirror(pair, origin=0.0), orientation=ident, translation=[0.0, 0.2, 0.0]),
         SDFIntersection([SDFRepeat(SDFSphere(radius=0.12), period=(0.5, 0.5, 0.5)),
                          A(SDFBox(halfsides=(1.2, 0.2, 1.2)), orientation=ident, translation=[0.0, -1.4, 0.0])]),
     ])

@@ -533,8 +533,10 @@ RM_DEV void user_end_bwd(S& s, const PT& P, int off, int type) {
 //     template <bool Fast> RM_DEV void   NAME_vjp(rm::V3 p, const float* theta, rm::V3 gq, rm::V3& gp, float* gtheta);
 //     template <bool Fast> RM_DEV float  NAME_out_fwd(float d, rm::V3 p, const float* theta);                      // optional pair
 //     template <bool Fast> RM_DEV void   NAME_out_vjp(float d, rm::V3 p, const float* theta, float g, float& gd, rm::V3& gp, float* gtheta);
-// and the dispatch user_warp_fwd / _vjp / _out_fwd / _out_vjp over the warp type.  The protocol is the affine pair's: PUSH
-// saves p on the frame stack and maps it, POP restores it; in reverse the POP enters the child frame again with gp = 0 and
+// and, optionally, the node's bound from its child's (extensions.py; #define RM_USER_WARP_BOUNDS when any type brings one)
+//     RM_DEV void NAME_bound(const float* theta, rm::LeafBound& b);                                               // child's in, node's out
+// and the dispatch user_warp_fwd / _vjp / _out_fwd / _out_vjp (/ user_warp_bound) over the warp type.  The protocol is the
+// affine pair's: PUSH saves p on the frame stack and maps it, POP restores it; in reverse the POP enters the child frame again with gp = 0 and
 // the PUSH pulls gp back through the map.  A type with an `out` keeps the child's value in a tape slot of its own (recorded
 // like the onion's input; the reverse pass only reads it, so vjp_replay finds it again).  Type, offset, parameter count and
 // slot are constants under StaticProgram: theta[] / gtheta[] are indexed by constants only and dissolve into registers.
@@ -1328,13 +1330,31 @@ RM_DEV void subtree_bound(GetIns ins, const float* P, int begin, int end, float*
       case RM_OP_USER_END: cx = cy = cz = 0.0f; R = Ru = inf; slope = uslope = 1.0f; break;
 #endif
 #ifdef RM_USER_WARPS
-      // a user warp signs no bound (yet): nothing is known about the node, whatever its child's sphere was.  Without the POP
-      // case the child's sphere would stay in place -- expressed in the CHILD's frame, yet standing for the warped node.
+      // a user warp without a NAME_bound signs no bound: nothing is known about the node, whatever its child's sphere was.
+      // Without the POP case the child's sphere would stay in place -- expressed in the CHILD's frame, yet standing for the
+      // warped node.
       case RM_OP_USER_PUSH:
         if (sp >= kDepth) { overflow = true; break; }
         st[sp].n = -2; st[sp].off = off; ++sp;
         break;
+#ifdef RM_USER_WARP_BOUNDS
+      // a warp that brings NAME_bound (aux0 = warp type): it is handed the child's bound, in the child's frame and with the
+      // clamps of this walk, and turns it into the node's own (its `out` included).  A type without one leaves `b` as
+      // "nothing known".  A bound the child did not have cannot be invented: R / Ru stay +inf where they were.
+      case RM_OP_USER_POP: {
+        --sp;
+        const bool lower = R < inf, upper = Ru < inf;
+        LeafBound b;
+        b.c = mk3(cx, cy, cz); b.R = R; b.slope = slope; b.Ru = Ru; b.uslope = uslope;
+        if (!user_warp_bound(w.z, P + off, b)) b = LeafBound();
+        cx = b.c.x; cy = b.c.y; cz = b.c.z;
+        R = lower ? b.R : inf; Ru = upper ? b.Ru : inf;
+        slope = (b.slope > 1.0f) ? 1.0f : b.slope;      // (as for RM_OP_USER: a NaN stays one and fails the checks at the end)
+        uslope = (b.uslope < 1.0f) ? 1.0f : b.uslope;
+      } break;
+#else
       case RM_OP_USER_POP: --sp; cx = cy = cz = 0.0f; R = Ru = inf; slope = uslope = 1.0f; break;
+#endif
 #endif
       default: break;            // nested CULL_MIN / CULL_LSE: no effect on the bound
     }

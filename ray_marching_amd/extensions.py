@@ -57,7 +57,16 @@ repetition, elongation: what neither a leaf, which has no child, nor a combinato
 ``gd = g df/dd``, ``gp += g df/dp``, ``gtheta[i] = g df/dtheta_i``.  ``p`` is the point in the node's own frame in all four.  The
 class keeps ``warp(points) -> points``, ``out(values, points) -> values`` where the source has the pair, and a ``forward`` that
 is ``out(child(warp(p)), p)``.  The field must stay a conservative distance (Lipschitz <= 1): that is the user's to see to, as
-for leaves.  A warp signs no bound: no cull test covers a subtree that contains one (culling inside its child is untouched).
+for leaves.  A warp may sign a bound too, with the leaf's signature and under its own NAME,
+
+    RM_DEV void NAME_bound(const float* theta, rm::LeafBound& b);
+
+but ``b`` ARRIVES holding the child's bound in the child's frame (``child(q) >= b.slope |q - b.c| - b.R`` and ``child(q) <= b.uslope
+|q - b.c| + b.Ru``, ``Ru = +inf`` where the child has none) and LEAVES holding the node's bound in the node's own frame, for the
+node's final value (its ``out`` included): ``node(p) >= slope' |p - c'| - R'`` with ``0.5 < slope' <= 1`` and, optionally, ``node(p) <=
+uslope' |p - c'| + Ru'``.  A scale maps the child's sphere, a mirror widens it; ``R = +inf`` says "no bound for these parameters",
+and a child without a bound keeps the node without one whatever the function writes.  Without the function no cull test covers
+a subtree that contains the warp (culling inside its child is untouched); ``check_bound`` takes a warp instance as well.
 
 User-defined *shaders* are the fourth kind, and the only one that is no scene node: ``register_shader`` teaches the frame kernels a
 per-pixel shader, passed to ``RenderLoop.forward`` (``capture``, ``training_step``, ``display_frame``) as ``mode``,
@@ -122,6 +131,7 @@ class UserWarp:
     sha1: str
     child: str          # attribute that holds the one child
     has_out: bool       # the source brings NAME_out_fwd / NAME_out_vjp (and the class an ``out`` method)
+    bounded: bool = False   # the source brings NAME_bound: cull tests may cover the node where its child is boundable too
 
 
 @dataclass(frozen=True)
@@ -202,20 +212,21 @@ def _shader_identifier(hip: str) -> str:
     return fwd.pop()
 
 
-def _has_bound(hip: str, name: str) -> bool:
-    """Whether the source defines ``RM_DEV void NAME_bound(`` (at most one, the leaf's own NAME, not a template)."""
+def _has_bound(hip: str, name: str, what: str = "leaf") -> bool:
+    """Whether the source defines ``RM_DEV void NAME_bound(`` (at most one, the own NAME of the leaf or warp, not a template)."""
     text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
     found = re.findall(r"(template\s*<[^<>]*>\s*)?RM_DEV\s+void\s+" + _DEF % "bound", text)
     if not found:
         return False
     want = f"`RM_DEV void {name}_bound(const float* theta, rm::LeafBound& b)`"
     if len(found) > 1:
-        raise ValueError(f"hip may define at most one bound function, {want} (found: {sorted(n for _, n in found)})")
+        raise ValueError(f"hip may define at most one bound function, {want}" + ("" if what == "leaf" else f" of the {what} {name!r}")
+                         + f" (found: {sorted(n for _, n in found)})")
     template, got = found[0]
     if got != name:
-        raise ValueError(f"the bound function of the leaf {name!r} must be {want}, found {got}_bound")
+        raise ValueError(f"the bound function of the {what} {name!r} must be {want}, found {got}_bound")
     if template:
-        raise ValueError(f"{want} must not be a template: a bound has no fast variant")
+        raise ValueError(f"{want}" + ("" if what == "leaf" else f" of the {what} {name!r}") + " must not be a template: a bound has no fast variant")
     return True
 
 
@@ -400,7 +411,8 @@ def register_warp(cls, *, params=(), hip: str, cost: int = 10, child: str = "sdf
         raise TypeError(f"register_warp: {cls.__name__} " + (
             f"has no out(values, points) method, but its source defines {name}_out_fwd / {name}_out_vjp" if has_out else
             f"has an out(values, points) method, but its source defines no {name}_out_fwd / {name}_out_vjp"))
-    spec = UserWarp(cls, name, params, hip, int(cost), hashlib.sha1(hip.encode()).hexdigest(), child, has_out)
+    spec = UserWarp(cls, name, params, hip, int(cost), hashlib.sha1(hip.encode()).hexdigest(), child, has_out,
+                    _has_bound(hip, name, "warp"))
     if spec.cost < 0:
         raise ValueError("register_warp: cost must be >= 0")
     old = _warps.get(cls)
@@ -505,15 +517,20 @@ def check_bound(leaf, extent: float = 4.0, n: int = 1 << 16, seed: int = 0):
 
     fails beyond ``1e-5 * (1 + |p| + R)`` -- the fp32 rounding of the value, a tenth of the margin the kernels add.
     Returns ``(centre, R, slope, Ru, uslope)``.  Run it once per leaf and for the parameter ranges you use: a wrong bound
-    gives silently wrong pixels."""
+    gives silently wrong pixels.
+
+    ``leaf`` may also be an instance of a registered warp, with its child: the node (map, child, ``out``) is what the kernels
+    evaluate at the same two point sets, and the bound is the node's, i.e. what ``NAME_bound`` made of the child's.  The child
+    must be boundable itself ("no finite bound" otherwise)."""
     import math
     from . import ops
     from .scene._base import SDFNode
-    spec = leaf_spec(leaf)
+    spec = leaf_spec(leaf) or warp_spec(leaf)
     if spec is None:
-        raise TypeError(f"check_bound: {type(leaf).__name__} is not a registered leaf")
+        raise TypeError(f"check_bound: {type(leaf).__name__} is not a registered leaf or warp")
     if not spec.bounded:
         raise ValueError(f"check_bound: the source of {type(leaf).__name__} defines no {spec.name}_bound")
+    value = f"{spec.name}_fwd(p)" if isinstance(spec, UserLeaf) else f"{type(leaf).__name__}(p)"
     params = list(leaf.parameters())
     dev = params[0].device if params else torch.device("cuda", torch.cuda.current_device())
     c, R, slope, Ru, uslope = ops.scene_bound(leaf, dev)
@@ -532,14 +549,14 @@ def check_bound(leaf, extent: float = 4.0, n: int = 1 << 16, seed: int = 0):
     pts = pts.cpu().double()
     dist = (pts - c.double()).norm(dim=-1)
     tol = 1e-5 * (1 + pts.norm(dim=-1) + abs(R))
-    checks = [("lower", f - (slope * dist - R) + tol, f"{spec.name}_fwd(p) >= {slope:g} |p - c| - {R:g}")]
+    checks = [("lower", f - (slope * dist - R) + tol, f"{value} >= {slope:g} |p - c| - {R:g}")]
     if math.isfinite(Ru):
-        checks.append(("upper", (uslope * dist + Ru) - f + tol, f"{spec.name}_fwd(p) <= {uslope:g} |p - c| + {Ru:g}"))
+        checks.append(("upper", (uslope * dist + Ru) - f + tol, f"{value} <= {uslope:g} |p - c| + {Ru:g}"))
     for which, margin, text in checks:
         bad = margin.isnan() | (margin < 0)
         if bad.any():
             i = int(torch.where(margin.isnan(), torch.full_like(margin, -math.inf), margin).argmin())
             raise ValueError(f"check_bound: the {which} bound of {type(leaf).__name__} fails at {int(bad.sum())} of {len(f)} points: "
-                             f"{text} with c = {c.tolist()} is off by {-float(margin[i] - tol[i]):.6g} at p = {pts[i].tolist()} "
-                             f"(value {float(f[i]):.6g})")
+                             f"{text}" + ("" if isinstance(spec, UserLeaf) else f" ({spec.name}_bound)") + f" with c = {c.tolist()} "
+                             f"is off by {-float(margin[i] - tol[i]):.6g} at p = {pts[i].tolist()} (value {float(f[i]):.6g})")
     return c, R, slope, Ru, uslope

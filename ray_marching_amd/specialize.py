@@ -139,7 +139,8 @@ def _combinator_section(cs: CompiledScene) -> str:
 
 def _warp_section(cs: CompiledScene) -> str:
     """User warp sources and the dispatch over the warp type (RM_OP_USER_PUSH / _POP: aux0), for the same first inclusion as
-    the leaf and combinator sections and independent of both.  The `out` switches list the types that bring one."""
+    the leaf and combinator sections and independent of both.  The `out` switches list the types that bring one, and so does
+    user_warp_bound, which exists (with RM_USER_WARP_BOUNDS) only where at least one type brings a NAME_bound."""
     types = cs.user_warps
     cases_f = "".join(f"    case {t}: return {name}_fwd<Fast>(p, theta);\n" for t, (name, _, _, _) in enumerate(types))
     cases_v = "".join(f"    case {t}: {name}_vjp<Fast>(p, theta, gq, gp, gtheta); break;\n" for t, (name, _, _, _) in enumerate(types))
@@ -148,6 +149,13 @@ def _warp_section(cs: CompiledScene) -> str:
                        for t, (name, _, out, _) in enumerate(types) if out)
     sources = "".join(f"// user warp {t}: {name}, {n} parameter floats, {'with' if out else 'no'} out, sha1 {sha}\n{src.strip()}\n"
                       for t, ((name, n, out, sha), src) in enumerate(zip(types, cs.user_warp_sources)))
+    # (only where a type brings NAME_bound: every other scene keeps the header, hence the library, it always had)
+    cases_b = "".join(f"    case {t}: {name}_bound(theta, b); return true;\n"
+                      for t, ((name, _, _, _), bounded) in enumerate(zip(types, cs.user_warp_bounded)) if bounded)
+    bound = "" if not cases_b else (
+        "#define RM_USER_WARP_BOUNDS 1\n"
+        "RM_DEV bool user_warp_bound(int type, const float* theta, LeafBound& b) {\n"
+        "  switch (type) {\n" + cases_b + "    default: return false;\n  }\n}\n")
     return (
         f"#define RM_USER_WARPS {len(types)}\n"
         f"#define RM_USER_WARP_MAX_PARAMS {max(1, max(n for _, n, _, _ in types))}\n"
@@ -160,7 +168,8 @@ def _warp_section(cs: CompiledScene) -> str:
         "  switch (type) {\n" + cases_of + "    default: return __builtin_nanf(\"\");\n  }\n}\n"
         "template <bool Fast> RM_DEV void user_warp_out_vjp(int type, float d, V3 p, const float* theta, float g, float& gd, V3& gp, "
         "float* gtheta) {\n"
-        "  switch (type) {\n" + cases_ov + "    default: break;\n  }\n}\n")
+        "  switch (type) {\n" + cases_ov + "    default: break;\n  }\n}\n"
+        + bound)
 
 
 def _shader_section(cs: CompiledScene) -> str:
@@ -411,6 +420,7 @@ def default_scenes():
         "make_many_primitive_scene32": R.make_many_primitive_scene(32),
         "carved_scene": make_carved_scene(),
         "warped_scene": make_warped_scene(),
+        "bounded_warped_scene": make_warped_scene(bounded=True),
     }
 
 
