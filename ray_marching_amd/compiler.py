@@ -22,6 +22,8 @@ import torch
 import torch.nn as nn
 
 from . import _abi
+from .extensions import (combinator_children, leaf_parameters, shader_parameters, shader_spec, user_spec,
+                         warp_child)
 
 import os
 
@@ -36,39 +38,27 @@ _CULL_MIN_CHILD_COST = 40
 # smooth unions with at least this many children get the exact logsumexp culling (RM_OP_CULL_LSE; the wave-wide test
 # costs ~45 instructions per evaluation whatever the number of children)
 _CULL_LSE_MIN_CHILDREN = 8
+# user types (RM_OP_USER*), per kind: what two instances with different parameter floats are "one" of, how many types a scene
+# holds at the most (None: no limit of its own), and what that message adds
+_USER_TYPES = {"leaf": ("type", None, ""), "combinator": ("class", 255, " ((class, children) pairs)"), "warp": ("class", 256, "")}
 
 
-def _user_leaf(node):
-    """Registration of a user-defined leaf (extensions.register_leaf), or None."""
-    from .extensions import leaf_spec
-    return leaf_spec(node) if getattr(node, "_rm_kind", None) is None else None
-
-
-def _user_combinator(node):
-    """Registration of a user-defined combinator (extensions.register_combinator), or None."""
-    from .extensions import combinator_spec
-    return combinator_spec(node) if getattr(node, "_rm_kind", None) is None else None
-
-
-def _user_warp(node):
-    """Registration of a user-defined domain operator (extensions.register_warp), or None."""
-    from .extensions import warp_spec
-    return warp_spec(node) if getattr(node, "_rm_kind", None) is None else None
+def _user(node):
+    """Registration of a user-defined leaf, combinator or warp (extensions.register_*) and its kind, or (None, None)."""
+    spec = user_spec(node) if getattr(node, "_rm_kind", None) is None else None
+    return spec, getattr(spec, "kind", None)
 
 
 def _cost(node) -> int:
     kind = getattr(node, "_rm_kind", None)
     if kind in _LEAF_COST:
         return _LEAF_COST[kind]
-    if kind is None and _user_leaf(node) is not None:
-        return _user_leaf(node).cost
-    if kind is None and _user_combinator(node) is not None:
-        from .extensions import combinator_children
-        spec = _user_combinator(node)
+    spec, user = _user(node)
+    if user == "leaf":
+        return spec.cost
+    if user == "combinator":
         return spec.cost + sum(_cost(c) + 1 for c in combinator_children(node, spec))
-    if kind is None and _user_warp(node) is not None:
-        from .extensions import warp_child
-        spec = _user_warp(node)
+    if user == "warp":
         return spec.cost + _cost(warp_child(node, spec))
     if kind == "affine":
         return 25 + _cost(node.sdf)
@@ -89,11 +79,10 @@ def _boundable(node) -> bool:
     kind = getattr(node, "_rm_kind", None)
     if kind in ("sphere", "box", "line", "disk", "torus"):
         return True
-    if kind is None and _user_leaf(node) is not None:
-        return _user_leaf(node).bounded
-    if kind is None and _user_warp(node) is not None:
-        from .extensions import warp_child
-        spec = _user_warp(node)
+    spec, user = _user(node)
+    if user == "leaf":
+        return spec.bounded
+    if user == "warp":
         return spec.bounded and _boundable(warp_child(node, spec))
     if kind in ("affine", "rounding", "onion"):
         return _boundable(node.sdf)
@@ -144,7 +133,7 @@ class CompiledScene:
         scenes with many parameters always uses the generic library (accumulators in LDS).
         ``precision="fast"`` selects the opt-in fast-arithmetic builds."""
         from . import specialize
-        if self.user_leaves or self.user_combinators or self.user_warps or self.user_shader:
+        if self.has_user_types:
             return self._user_leaf_lib(backward, precision)
         generic = _abi.generic_lib(precision)
         if backward and not specialize.static_backward(self):
@@ -170,18 +159,20 @@ class CompiledScene:
         if precision == "exact" and self._lib is not None:
             return self._lib
         lib = specialize.load_user(self, precision)
-        if lib.rm_user_leaves() != len(self.user_leaves):
-            raise _abi.RmError(f"{lib._name} was built with {lib.rm_user_leaves()} user leaf types, the scene has {len(self.user_leaves)}")
-        if lib.rm_user_combinators() != len(self.user_combinators):
-            raise _abi.RmError(f"{lib._name} was built with {lib.rm_user_combinators()} user combinator types, the scene has "
-                               f"{len(self.user_combinators)}")
-        if lib.rm_user_warps() != len(self.user_warps):
-            raise _abi.RmError(f"{lib._name} was built with {lib.rm_user_warps()} user warp types, the scene has {len(self.user_warps)}")
-        if lib.rm_user_shaders() != len(self.user_shader[:1]):
-            raise _abi.RmError(f"{lib._name} was built with {lib.rm_user_shaders()} user shaders, the program has {len(self.user_shader[:1])}")
+        for built, have, what in ((lib.rm_user_leaves(), self.user_leaves, "user leaf types, the scene"),
+                                  (lib.rm_user_combinators(), self.user_combinators, "user combinator types, the scene"),
+                                  (lib.rm_user_warps(), self.user_warps, "user warp types, the scene"),
+                                  (lib.rm_user_shaders(), self.user_shader[:1], "user shaders, the program")):
+            if built != len(have):
+                raise _abi.RmError(f"{lib._name} was built with {built} {what} has {len(have)}")
         if precision == "exact":
             self._lib = lib
         return lib
+
+    @property
+    def has_user_types(self) -> bool:
+        """User-defined leaves, combinators or warps in the scene, or a user shader on it: no interpreter path (_user_leaf_lib)."""
+        return bool(self.user_leaves or self.user_combinators or self.user_warps or self.user_shader)
 
     @property
     def specialised(self) -> bool:
@@ -290,11 +281,9 @@ class _Emitter:
         # (default: also with the minimum of its children's own bounds, rm_device.h: cull_union_children)
         self.cull_union_table = os.environ.get("RM_CULL_UNION_TABLE", "1") != "0"
         self.want_table = False        # set by the parent union for the child it emits next
-        self.user_types = []           # extensions.UserLeaf of every user leaf type, in order of first appearance (= aux0)
-        self.user_floats = []          # ... and its parameter floats (= aux1)
-        self.comb_types = []           # (extensions.UserCombinator, children, parameter floats) per combinator type, first appearance
-        self.warp_types = []           # extensions.UserWarp of every warp type, in order of first appearance (= aux0)
-        self.warp_floats = []          # ... and its parameter floats
+        # the user types of each kind -> type index, in order of first appearance: (extensions.UserLeaf, parameter floats),
+        # (extensions.UserCombinator, children, parameter floats), (extensions.UserWarp, parameter floats)
+        self.user_types = {kind: {} for kind in _USER_TYPES}
 
     def off(self, *params):
         """Offset of the first parameter; the rest must follow contiguously."""
@@ -306,6 +295,18 @@ class _Emitter:
                                  "order (shared nn.Parameter between fields of one node is not supported)")
             expect += p.numel()
         return base
+
+    def user_type(self, node, spec, *shape, floats):
+        """Index of the type (spec, *shape, floats) among the user types of its kind, entered on first appearance."""
+        types, (unit, limit, note) = self.user_types[spec.kind], _USER_TYPES[spec.kind]
+        if any(key[0] is spec and key[-1] != floats for key in types):
+            raise ValueError(f"{type(node).__name__}: instances of one user {spec.kind} {unit} must have the same number of parameter floats")
+        key = (spec, *shape, floats)
+        if key not in types:
+            if limit is not None and len(types) >= limit:
+                raise ValueError(f"a scene holds at most {limit} user {spec.kind} types{note}")
+            types[key] = len(types)
+        return types[key]
 
     def push(self, n):
         self.depth += n
@@ -319,8 +320,8 @@ class _Emitter:
 
 
 def _emit(node, em: _Emitter, n_params: int):
-    from .extensions import leaf_parameters
     kind = getattr(node, "_rm_kind", None)
+    spec, user = _user(node)
     A = _abi
     if kind == "sphere":
         em.ins(A.OP_SPHERE, em.off(node.radius))
@@ -420,19 +421,11 @@ def _emit(node, em: _Emitter, n_params: int):
         slot = em.n_slots
         em.n_slots += 1
         em.ins(A.OP_ONION, em.off(node.radius), slot)
-    elif kind is None and _user_leaf(node) is not None:
-        spec = _user_leaf(node)
+    elif user == "leaf":
         params = leaf_parameters(node, spec)
         n = sum(p.numel() for p in params)
-        if spec not in em.user_types:
-            em.user_types.append(spec)
-            em.user_floats.append(n)
-        if em.user_floats[em.user_types.index(spec)] != n:
-            raise ValueError(f"{type(node).__name__}: instances of one user leaf type must have the same number of parameter floats")
-        em.ins(A.OP_USER, em.off(*params) if params else 0, em.user_types.index(spec), n)
-    elif kind is None and _user_combinator(node) is not None:
-        from .extensions import combinator_children
-        spec = _user_combinator(node)
+        em.ins(A.OP_USER, em.off(*params) if params else 0, em.user_type(node, spec, floats=n), n)
+    elif user == "combinator":
         kids = combinator_children(node, spec)
         n = len(kids)
         if n > A.USER_COMB_MAX_CHILDREN:
@@ -440,14 +433,7 @@ def _emit(node, em: _Emitter, n_params: int):
                              f"(RM_USER_COMB_MAX_CHILDREN), this one has {n}; nest it")
         params = leaf_parameters(node, spec)
         floats = sum(p.numel() for p in params)
-        for other, _, other_floats in em.comb_types:
-            if other is spec and other_floats != floats:
-                raise ValueError(f"{type(node).__name__}: instances of one user combinator class must have the same number of parameter floats")
-        key = (spec, n, floats)
-        if key not in em.comb_types:
-            if len(em.comb_types) >= 255:
-                raise ValueError("a scene holds at most 255 user combinator types ((class, children) pairs)")
-            em.comb_types.append(key)
+        t = em.user_type(node, spec, n, floats=floats)
         # n value slots, then n slots for the children's upstream gradients (the reverse pass leaves the values in place)
         base = em.n_slots
         em.n_slots += 2 * n
@@ -455,21 +441,12 @@ def _emit(node, em: _Emitter, n_params: int):
         for i, child in enumerate(kids):
             _emit(child, em, n_params)
             em.ins(A.OP_USER_FOLD, 0, base + i, base + n + i)
-        em.ins(A.OP_USER_END, em.off(*params) if params else 0, base, (floats << 16) | (em.comb_types.index(key) << 8) | n)
-    elif kind is None and _user_warp(node) is not None:
-        from .extensions import warp_child
-        spec = _user_warp(node)
+        em.ins(A.OP_USER_END, em.off(*params) if params else 0, base, (floats << 16) | (t << 8) | n)
+    elif user == "warp":
         kid = warp_child(node, spec)
         params = leaf_parameters(node, spec)
         floats = sum(p.numel() for p in params)
-        if spec not in em.warp_types:
-            if len(em.warp_types) >= 256:
-                raise ValueError("a scene holds at most 256 user warp types")
-            em.warp_types.append(spec)
-            em.warp_floats.append(floats)
-        t = em.warp_types.index(spec)
-        if em.warp_floats[t] != floats:
-            raise ValueError(f"{type(node).__name__}: instances of one user warp class must have the same number of parameter floats")
+        t = em.user_type(node, spec, floats=floats)
         if floats > 32767:
             raise ValueError(f"{type(node).__name__}: a user warp takes at most 32767 parameter floats")
         off = em.off(*params) if params else 0
@@ -506,7 +483,6 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
         cursor += p.numel()
     shader_offset, user_shader, shader_source = cursor, (), ""
     if shader is not None:
-        from .extensions import shader_parameters, shader_spec
         spec = shader_spec(shader)
         if spec is None:
             raise TypeError(f"{type(shader).__name__} is not a registered shader (extensions.register_shader)")
@@ -529,28 +505,24 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
     rc = _abi.lib.rm_validate_program(program.ctypes.data, program.shape[0], n_params, em.n_derived,
                                       em.max_depth, em.n_slots)
     _abi.check(rc, "rm_validate_program")
-    signature = (tuple(map(tuple, program.tolist())), n_params, em.n_derived, em.max_depth, em.n_slots, em.n_grad_derived)
-    user_leaves = tuple((u.name, em.user_floats[t], u.sha1) for t, u in enumerate(em.user_types))
-    if user_leaves:
-        signature = signature + (user_leaves,)      # (scenes of built-in nodes keep the signature they always had)
-    user_combinators = tuple((u.name, n, floats, u.sha1) for u, n, floats in em.comb_types)
-    if user_combinators:
-        if not user_leaves:
-            signature = signature + ((),)           # (signature[-2] stays the user leaves)
-        signature = signature + (user_combinators,)
-    comb_sources = tuple({u.name: u.hip for u, _, _ in em.comb_types}.values())
-    user_warps = tuple((u.name, em.warp_floats[t], u.has_out, u.sha1) for t, u in enumerate(em.warp_types))
-    if user_warps:
-        signature = signature + ((),) * (8 - len(signature)) + (user_warps,)      # (signature[-3], [-2] stay leaves, combinators)
-    if user_shader:
-        signature = signature + ((),) * (9 - len(signature)) + (user_shader,)     # (signature[6:9] stay leaves, combinators, warps)
+    leaf_types, comb_types, warp_types = (tuple(em.user_types[k]) for k in ("leaf", "combinator", "warp"))
+    user_leaves = tuple((u.name, floats, u.sha1) for u, floats in leaf_types)
+    user_combinators = tuple((u.name, n, floats, u.sha1) for u, n, floats in comb_types)
+    user_warps = tuple((u.name, floats, u.has_out, u.sha1) for u, floats in warp_types)
+    # the six entries every scene has, then one slot per kind of user code with the trailing empty ones dropped: scenes of built-in
+    # nodes keep the signature they always had, and signature[6:] reads (leaves, combinators, warps, shader) as far as it goes
+    slots = [user_leaves, user_combinators, user_warps, user_shader]
+    while slots and not slots[-1]:
+        slots.pop()
+    signature = (tuple(map(tuple, program.tolist())), n_params, em.n_derived, em.max_depth, em.n_slots, em.n_grad_derived, *slots)
     return CompiledScene(program=program, leaves=leaves, leaf_names=names, leaf_offsets=offsets,
                          n_params=n_params, n_derived=em.n_derived, n_grad_derived=em.n_grad_derived, stack_floats=em.max_depth,
                          n_slots=em.n_slots, signature=signature, user_leaves=user_leaves,
-                         user_sources=tuple(u.hip for u in em.user_types), user_bounded=tuple(u.bounded for u in em.user_types),
-                         user_combinators=user_combinators, user_combinator_sources=comb_sources,
-                         user_warps=user_warps, user_warp_sources=tuple(u.hip for u in em.warp_types),
-                         user_warp_bounded=tuple(u.bounded for u in em.warp_types),
+                         user_sources=tuple(u.hip for u, _ in leaf_types), user_bounded=tuple(u.bounded for u, _ in leaf_types),
+                         user_combinators=user_combinators,
+                         user_combinator_sources=tuple({u.name: u.hip for u, _, _ in comb_types}.values()),
+                         user_warps=user_warps, user_warp_sources=tuple(u.hip for u, _ in warp_types),
+                         user_warp_bounded=tuple(u.bounded for u, _ in warp_types),
                          user_shader=user_shader, user_shader_source=shader_source, shader_offset=shader_offset)
 
 

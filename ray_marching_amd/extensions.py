@@ -100,34 +100,35 @@ __all__ = ["register_leaf", "leaf_spec", "check_bound", "UserLeaf", "register_co
 
 
 @dataclass(frozen=True)
-class UserLeaf:
+class _UserSpec:
+    """What the four kinds of registration share.  ``sha1`` (of the source) is part of the scene signature, hence of the library
+    hash; ``cost`` (not for shaders) is the VALU estimate of the node's own code, to which compiler._cost adds its children's."""
     cls: type
-    name: str           # NAME of NAME_fwd / NAME_vjp
-    params: tuple       # attribute names of the nn.Parameters, named_parameters() order
+    name: str           # NAME of NAME_fwd / NAME_vjp (/ NAME_out_fwd / NAME_out_vjp / NAME_bound)
+    params: tuple       # attribute names of the node's own nn.Parameters, named_parameters() order
     hip: str
-    cost: int           # VALU estimate per evaluation (compiler._cost)
-    sha1: str           # of the source: part of the scene signature, hence of the library hash
+
+
+@dataclass(frozen=True)
+class UserLeaf(_UserSpec):
+    kind = "leaf"
+    cost: int
+    sha1: str
     bounded: bool = False   # the source brings NAME_bound: cull tests may cover the leaf (read from the source, like NAME)
 
 
 @dataclass(frozen=True)
-class UserCombinator:
-    cls: type
-    name: str           # NAME of NAME_fwd / NAME_vjp
-    params: tuple       # attribute names of the node's own nn.Parameters, named_parameters() order
-    hip: str
-    cost: int           # VALU estimate of the fold itself (compiler._cost adds the children's)
+class UserCombinator(_UserSpec):
+    kind = "combinator"
+    cost: int
     sha1: str
     children: str       # attribute that holds the children (an nn.ModuleList or sequence of SDF modules)
 
 
 @dataclass(frozen=True)
-class UserWarp:
-    cls: type
-    name: str           # NAME of NAME_fwd / NAME_vjp (/ NAME_out_fwd / NAME_out_vjp)
-    params: tuple       # attribute names of the node's own nn.Parameters, named_parameters() order
-    hip: str
-    cost: int           # VALU estimate of the map (and the `out`) itself (compiler._cost adds the child's)
+class UserWarp(_UserSpec):
+    kind = "warp"
+    cost: int
     sha1: str
     child: str          # attribute that holds the one child
     has_out: bool       # the source brings NAME_out_fwd / NAME_out_vjp (and the class an ``out`` method)
@@ -135,86 +136,89 @@ class UserWarp:
 
 
 @dataclass(frozen=True)
-class UserShader:
-    cls: type
-    name: str           # NAME of NAME_fwd / NAME_vjp
-    params: tuple       # attribute names of the shader's nn.Parameters, named_parameters() order
-    hip: str
+class UserShader(_UserSpec):
+    kind = "shader"
     sha1: str
 
 
-_registry: dict[type, UserLeaf] = {}
-_combinators: dict[type, UserCombinator] = {}
-_warps: dict[type, UserWarp] = {}
-_shaders: dict[type, UserShader] = {}
+@dataclass(frozen=True)
+class _Kind:
+    """What tells one kind of user-defined code from another at registration: a row of _KINDS, walked by _register."""
+    spec: type              # the dataclass of its registrations
+    ret: str                # regex of NAME_fwd's return type
+    signature: str          # the fwd / vjp pair, as the error message of a source without it quotes them
+    methods: tuple = ()     # (name, as the error message writes it) of the Python methods the class must have
+    attr: str = ""          # the argument that names the attribute with the children ...
+    holds: str = ""         # ... and what the message says the attribute holds
+    same: tuple = ("sha1", "params")                # fields a second registration of the class must repeat ...
+    different: str = "source or parameters"         # ... and how the message lists them
+    device_forward: bool = True     # forward() is replaced by _device_forward (a shader keeps its own)
+    out_pair: bool = False          # the source may bring NAME_out_fwd / NAME_out_vjp
+    bound: str = ""                 # the noun under which NAME_bound is looked for ("": the kind signs no bound)
+
+
+_KINDS = {
+    "leaf": _Kind(
+        UserLeaf, "float",
+        "exactly two device functions, `template <bool Fast> RM_DEV float NAME_fwd(rm::V3 p, const float* theta)` and `template "
+        "<bool Fast> RM_DEV void NAME_vjp(rm::V3 p, const float* theta, float g, rm::V3& gp, float* gtheta)`",
+        same=("sha1", "params", "cost"), different="source, parameters or cost", bound="leaf"),
+    "combinator": _Kind(
+        UserCombinator, "float",
+        "exactly two device functions, `template <bool Fast, int N> RM_DEV float NAME_fwd(const float (&d)[N], const float* theta)` "
+        "and `template <bool Fast, int N> RM_DEV void NAME_vjp(const float (&d)[N], const float* theta, float g, float (&gd)[N], "
+        "float* gtheta)`",
+        methods=(("combine", "combine(values [..., n]) -> [..., 1] method"),), attr="children", holds="child modules",
+        same=("sha1", "params", "cost", "children"), different="source, parameters, cost or children attribute"),
+    "warp": _Kind(
+        UserWarp, r"(?:rm::)?V3",
+        "`template <bool Fast> RM_DEV rm::V3 NAME_fwd(rm::V3 p, const float* theta)` and `template <bool Fast> RM_DEV void "
+        "NAME_vjp(rm::V3 p, const float* theta, rm::V3 gq, rm::V3& gp, float* gtheta)`",
+        methods=(("warp", "warp(points [..., 3]) -> [..., 3] method"),), attr="child", holds="child module",
+        same=("sha1", "params", "cost", "child"), different="source, parameters, cost or child attribute",
+        out_pair=True, bound="warp"),
+    "shader": _Kind(
+        UserShader, r"(?:rm::)?V3",
+        "exactly two device functions, `template <bool Fast> RM_DEV rm::V3 NAME_fwd(const rm::ShadeIn& s, const float* theta)` and "
+        "`template <bool Fast> RM_DEV void NAME_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 g, rm::ShadeGrad& gs, float* "
+        "gtheta)`",
+        methods=(("forward", "forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals)"),),
+        device_forward=False),
+}
+
+_registry: dict[type, _UserSpec] = {}       # registered class -> its registration, of whichever kind
 
 _DEF = r"\b([A-Za-z_]\w*)_%s\s*\("
 
 
-def _identifier(hip: str) -> str:
+def _parse(kind: str, hip: str):
+    """(NAME, has_out, bounded) of the source of a ``kind``.  NAME is that of the one ``NAME_fwd`` with the kind's return type and
+    must be that of the ``NAME_vjp`` too (of one of them where the kind may bring ``NAME_out_fwd`` / ``NAME_out_vjp``, which come
+    as a pair or not at all and are looked up by their full names, like NAME_bound)."""
+    row = _KINDS[kind]
     text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
-    fwd, vjp = (set(re.findall(r"RM_DEV\s+%s\s+" % ret + _DEF % kind, text)) for ret, kind in (("float", "fwd"), ("void", "vjp")))
-    if len(fwd) != 1 or fwd != vjp:
-        raise ValueError("hip must define exactly two device functions, `template <bool Fast> RM_DEV float NAME_fwd(rm::V3 p, "
-                         "const float* theta)` and `template <bool Fast> RM_DEV void NAME_vjp(rm::V3 p, const float* theta, "
-                         f"float g, rm::V3& gp, float* gtheta)`, with one NAME (found fwd: {sorted(fwd)}, vjp: {sorted(vjp)})")
-    if re.search(r"\basm\b|__asm", text):
-        raise ValueError("a user leaf must not contain inline assembly (INTEGRATION.md: leaf contract)")
-    return fwd.pop()
 
+    def names(ret, fn):
+        return set(re.findall(r"RM_DEV\s+%s\s+" % ret + _DEF % fn, text))
 
-def _combinator_identifier(hip: str) -> str:
-    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
-    fwd, vjp = (set(re.findall(r"RM_DEV\s+%s\s+" % ret + _DEF % kind, text)) for ret, kind in (("float", "fwd"), ("void", "vjp")))
-    if len(fwd) != 1 or fwd != vjp:
-        raise ValueError("hip must define exactly two device functions, `template <bool Fast, int N> RM_DEV float NAME_fwd(const "
-                         "float (&d)[N], const float* theta)` and `template <bool Fast, int N> RM_DEV void NAME_vjp(const float "
-                         f"(&d)[N], const float* theta, float g, float (&gd)[N], float* gtheta)`, with one NAME (found fwd: "
-                         f"{sorted(fwd)}, vjp: {sorted(vjp)})")
-    if re.search(r"\basm\b|__asm", text):
-        raise ValueError("a user combinator must not contain inline assembly (INTEGRATION.md: combinator contract)")
-    return fwd.pop()
-
-
-def _warp_identifier(hip: str):
-    """(NAME, has_out) of a warp source.  NAME is that of the one V3-returning ``NAME_fwd``; ``NAME_vjp`` must be there, and
-    ``NAME_out_fwd`` / ``NAME_out_vjp`` come as a pair or not at all (looked up by their full names, like NAME_bound)."""
-    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
-    fwd = set(re.findall(r"RM_DEV\s+(?:rm::)?V3\s+" + _DEF % "fwd", text))
+    fwd, vjp = names(row.ret, "fwd"), names("void", "vjp")
     name = next(iter(fwd)) if len(fwd) == 1 else None
-
-    def defines(ret, fn):
-        return re.search(r"RM_DEV\s+%s\s+%s\s*\(" % (ret, re.escape(fn)), text) is not None
-
-    if name is None or not defines("void", f"{name}_vjp"):
-        raise ValueError("hip must define `template <bool Fast> RM_DEV rm::V3 NAME_fwd(rm::V3 p, const float* theta)` and `template "
-                         "<bool Fast> RM_DEV void NAME_vjp(rm::V3 p, const float* theta, rm::V3 gq, rm::V3& gp, float* gtheta)`, with "
-                         f"one NAME (found fwd: {sorted(fwd)})")
-    out_fwd, out_vjp = defines("float", f"{name}_out_fwd"), defines("void", f"{name}_out_vjp")
+    if name is None or (name not in vjp if row.out_pair else vjp != fwd):
+        raise ValueError(f"hip must define {row.signature}, with one NAME (found fwd: {sorted(fwd)}"
+                         + ("" if row.out_pair else f", vjp: {sorted(vjp)}") + ")")
+    out_fwd, out_vjp = row.out_pair and f"{name}_out" in names("float", "fwd"), row.out_pair and f"{name}_out" in vjp
     if out_fwd != out_vjp:
         raise ValueError(f"hip may define `template <bool Fast> RM_DEV float {name}_out_fwd(float d, rm::V3 p, const float* theta)` and "
                          f"`template <bool Fast> RM_DEV void {name}_out_vjp(float d, rm::V3 p, const float* theta, float g, float& gd, "
                          f"rm::V3& gp, float* gtheta)`: both or neither (found {name}_out_fwd: {out_fwd}, {name}_out_vjp: {out_vjp})")
     if re.search(r"\basm\b|__asm", text):
-        raise ValueError("a user warp must not contain inline assembly (INTEGRATION.md: warp contract)")
-    return name, out_fwd
+        raise ValueError(f"a user {kind} must not contain inline assembly (INTEGRATION.md: {kind} contract)")
+    return name, out_fwd, bool(row.bound) and _has_bound(text, name, row.bound)
 
 
-def _shader_identifier(hip: str) -> str:
-    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
-    fwd, vjp = (set(re.findall(r"RM_DEV\s+%s\s+" % ret + _DEF % kind, text)) for ret, kind in ((r"(?:rm::)?V3", "fwd"), ("void", "vjp")))
-    if len(fwd) != 1 or fwd != vjp:
-        raise ValueError("hip must define exactly two device functions, `template <bool Fast> RM_DEV rm::V3 NAME_fwd(const rm::ShadeIn& s, "
-                         "const float* theta)` and `template <bool Fast> RM_DEV void NAME_vjp(const rm::ShadeIn& s, const float* theta, "
-                         f"rm::V3 g, rm::ShadeGrad& gs, float* gtheta)`, with one NAME (found fwd: {sorted(fwd)}, vjp: {sorted(vjp)})")
-    if re.search(r"\basm\b|__asm", text):
-        raise ValueError("a user shader must not contain inline assembly (INTEGRATION.md: shader contract)")
-    return fwd.pop()
-
-
-def _has_bound(hip: str, name: str, what: str = "leaf") -> bool:
-    """Whether the source defines ``RM_DEV void NAME_bound(`` (at most one, the own NAME of the leaf or warp, not a template)."""
-    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
+def _has_bound(text: str, name: str, what: str) -> bool:
+    """Whether the source (``text``: without its comments) defines ``RM_DEV void NAME_bound(`` (at most one, the own NAME of the
+    leaf or warp, not a template)."""
     found = re.findall(r"(template\s*<[^<>]*>\s*)?RM_DEV\s+void\s+" + _DEF % "bound", text)
     if not found:
         return False
@@ -231,8 +235,8 @@ def _has_bound(hip: str, name: str, what: str = "leaf") -> bool:
 
 
 def _device_forward(self, *args, **kwargs):
-    """forward() installed by register_leaf: CUDA points go to the HIP evaluator (the leaf as a one-node scene), anything
-    else to the class's own PyTorch forward."""
+    """forward() installed by register_leaf / register_combinator / register_warp: CUDA points go to the HIP evaluator (the node as
+    a scene of its own), anything else to the class's own PyTorch forward."""
     points = args[0] if args else next(iter(kwargs.values()))
     if isinstance(points, torch.Tensor) and points.is_cuda:
         from .scene._base import SDFNode
@@ -240,7 +244,7 @@ def _device_forward(self, *args, **kwargs):
     return type(self)._rm_torch_forward(self, *args, **kwargs)
 
 
-def _torch_forward(cls):
+def _torch_forward(cls, fn: str):
     """The PyTorch forward of ``cls``: the first one in its MRO that is not the forward installed here (a subclass of a
     registered class inherits _device_forward; its base keeps the original under _rm_torch_forward)."""
     for c in cls.__mro__:
@@ -249,15 +253,68 @@ def _torch_forward(cls):
             f = c.__dict__["_rm_torch_forward"]
         if f is not None:
             return f
-    raise TypeError(f"register_leaf: {cls.__name__} has no forward")
+    raise TypeError(f"{fn}: {cls.__name__} has no forward")
 
 
-def _registered_class(cls, registry=None):
-    registry = _registry if registry is None else registry
-    for c in cls.__mro__:
-        if c in registry:
-            return c
-    return None
+def _registrations(cls):
+    """The registrations of ``cls`` and of its ancestors, nearest first."""
+    return (_registry[c] for c in cls.__mro__ if c in _registry)
+
+
+def user_spec(node, kind: str = None):
+    """The registration of this module's class (or of the nearest registered class it derives from), of whichever kind or, with
+    ``kind``, where it is of that one; else None."""
+    spec = next(_registrations(type(node)), None)
+    return spec if spec is not None and kind in (None, spec.kind) else None
+
+
+def _register(kind: str, cls, *, params, hip: str, **own):
+    """What the four ``register_*`` do, in one order of checks: the class, its kind, its methods and child attribute, the parameter
+    names, the source, the cost, a second registration of the class, the identifier.  ``own``: the arguments only some kinds
+    take (``cost``, ``children`` / ``child``), under the names of the fields they become."""
+    row, fn = _KINDS[kind], f"register_{kind}"
+    if not (isinstance(cls, type) and issubclass(cls, nn.Module)):
+        raise TypeError(f"{fn}: {cls!r} is not an nn.Module subclass")
+    if getattr(cls, "_rm_kind", None) is not None:
+        raise TypeError(f"{fn}: {cls.__name__} is already a ray_marching_amd node")
+    for other in _registrations(cls):
+        if other.kind != kind:
+            raise TypeError(f"{fn}: {cls.__name__} is already registered as a {other.kind}")
+    for method, text in row.methods:
+        if not callable(getattr(cls, method, None)) or getattr(cls, method) is getattr(nn.Module, method, None):
+            raise TypeError(f"{fn}: {cls.__name__} has no {text}")
+    if row.attr and (not isinstance(own[row.attr], str) or not own[row.attr]):
+        raise ValueError(f"{fn}: {row.attr} must name the attribute that holds the {row.holds}")
+    params = tuple(params)
+    if not all(isinstance(p, str) for p in params) or len(set(params)) != len(params):
+        raise ValueError(f"{fn}: params must be distinct attribute names")
+    name, has_out, bounded = _parse(kind, hip)
+    if row.out_pair and has_out != callable(getattr(cls, "out", None)):
+        raise TypeError(f"{fn}: {cls.__name__} " + (
+            f"has no out(values, points) method, but its source defines {name}_out_fwd / {name}_out_vjp" if has_out else
+            f"has an out(values, points) method, but its source defines no {name}_out_fwd / {name}_out_vjp"))
+    if "cost" in own:
+        own["cost"] = int(own["cost"])
+        if own["cost"] < 0:
+            raise ValueError(f"{fn}: cost must be >= 0")
+    if row.out_pair:
+        own["has_out"] = has_out
+    if row.bound:
+        own["bounded"] = bounded
+    spec = row.spec(cls=cls, name=name, params=params, hip=hip, sha1=hashlib.sha1(hip.encode()).hexdigest(), **own)
+    old = _registry.get(cls)
+    if old is not None:
+        if any(getattr(old, f) != getattr(spec, f) for f in row.same):
+            raise ValueError(f"{fn}: {cls.__name__} is already registered with different {row.different}")
+        return cls
+    for other in _registry.values():
+        if other.name == spec.name:          # (a scene's user types and the shader are compiled into one translation unit)
+            raise ValueError(f"{fn}: the identifier {spec.name!r} is already used by {other.cls.__name__}")
+    if row.device_forward:
+        cls._rm_torch_forward = _torch_forward(cls, fn)
+        cls.forward = _device_forward
+    _registry[cls] = spec
+    return cls
 
 
 def register_leaf(cls, *, params, hip: str, cost: int):
@@ -268,42 +325,14 @@ def register_leaf(cls, *, params, hip: str, cost: int):
     cost:   VALU instructions per evaluation, roughly (a sphere is 13, a torus 24); only steers cull placement.
 
     Registering a class again with the same source is a no-op; with other source, parameters or cost it is an error
-    (libraries already built from the first registration would no longer describe the class)."""
-    if not (isinstance(cls, type) and issubclass(cls, nn.Module)):
-        raise TypeError(f"register_leaf: {cls!r} is not an nn.Module subclass")
-    if getattr(cls, "_rm_kind", None) is not None:
-        raise TypeError(f"register_leaf: {cls.__name__} is already a ray_marching_amd node")
-    params = tuple(params)
-    if not all(isinstance(p, str) for p in params) or len(set(params)) != len(params):
-        raise ValueError("register_leaf: params must be distinct attribute names")
-    name = _identifier(hip)
-    spec = UserLeaf(cls, name, params, hip, int(cost), hashlib.sha1(hip.encode()).hexdigest(), _has_bound(hip, name))
-    if spec.cost < 0:
-        raise ValueError("register_leaf: cost must be >= 0")
-    old = _registry.get(cls)
-    if old is not None:
-        if (old.sha1, old.params, old.cost) != (spec.sha1, spec.params, spec.cost):
-            raise ValueError(f"register_leaf: {cls.__name__} is already registered with different source, parameters or cost")
-        return cls
-    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()) + list(_shaders.values()):
-        if other.name == spec.name:          # (the user types of one scene are compiled into one translation unit)
-            raise ValueError(f"register_leaf: the identifier {spec.name!r} is already used by {other.cls.__name__}")
-    if _registered_class(cls, _combinators) is not None:
-        raise TypeError(f"register_leaf: {cls.__name__} is already registered as a combinator")
-    if _registered_class(cls, _warps) is not None:
-        raise TypeError(f"register_leaf: {cls.__name__} is already registered as a warp")
-    if _registered_class(cls, _shaders) is not None:
-        raise TypeError(f"register_leaf: {cls.__name__} is already registered as a shader")
-    cls._rm_torch_forward = _torch_forward(cls)
-    cls.forward = _device_forward
-    _registry[cls] = spec
-    return cls
+    (libraries already built from the first registration would no longer describe the class).  Identifiers are unique
+    across all four kinds (leaves, combinators, warps and shaders)."""
+    return _register("leaf", cls, params=params, hip=hip, cost=cost)
 
 
 def leaf_spec(node):
     """The registration of this module's class (or of the registered class it derives from), or None."""
-    c = _registered_class(type(node))
-    return None if c is None else _registry[c]
+    return user_spec(node, "leaf")
 
 
 def register_combinator(cls, *, params=(), hip: str, cost: int = 4, children: str = "sdfs"):
@@ -320,47 +349,13 @@ def register_combinator(cls, *, params=(), hip: str, cost: int = 4, children: st
     children and calls it.  Registration installs the same dispatch as ``register_leaf``: CUDA points go to the HIP
     evaluator, anything else to the class's own forward (kept under ``_rm_torch_forward``).  Registering a class again with
     the same source is a no-op; with other source, parameters, cost or children attribute it is an error.  Identifiers are
-    unique across leaves and combinators."""
-    if not (isinstance(cls, type) and issubclass(cls, nn.Module)):
-        raise TypeError(f"register_combinator: {cls!r} is not an nn.Module subclass")
-    if getattr(cls, "_rm_kind", None) is not None:
-        raise TypeError(f"register_combinator: {cls.__name__} is already a ray_marching_amd node")
-    if not callable(getattr(cls, "combine", None)):
-        raise TypeError(f"register_combinator: {cls.__name__} has no combine(values [..., n]) -> [..., 1] method")
-    if not isinstance(children, str) or not children:
-        raise ValueError("register_combinator: children must name the attribute that holds the child modules")
-    params = tuple(params)
-    if not all(isinstance(p, str) for p in params) or len(set(params)) != len(params):
-        raise ValueError("register_combinator: params must be distinct attribute names")
-    name = _combinator_identifier(hip)
-    spec = UserCombinator(cls, name, params, hip, int(cost), hashlib.sha1(hip.encode()).hexdigest(), children)
-    if spec.cost < 0:
-        raise ValueError("register_combinator: cost must be >= 0")
-    old = _combinators.get(cls)
-    if old is not None:
-        if (old.sha1, old.params, old.cost, old.children) != (spec.sha1, spec.params, spec.cost, spec.children):
-            raise ValueError(f"register_combinator: {cls.__name__} is already registered with different source, parameters, "
-                             "cost or children attribute")
-        return cls
-    if _registered_class(cls) is not None:
-        raise TypeError(f"register_combinator: {cls.__name__} is already registered as a leaf")
-    if _registered_class(cls, _warps) is not None:
-        raise TypeError(f"register_combinator: {cls.__name__} is already registered as a warp")
-    if _registered_class(cls, _shaders) is not None:
-        raise TypeError(f"register_combinator: {cls.__name__} is already registered as a shader")
-    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()) + list(_shaders.values()):
-        if other.name == spec.name:
-            raise ValueError(f"register_combinator: the identifier {spec.name!r} is already used by {other.cls.__name__}")
-    cls._rm_torch_forward = _torch_forward(cls)
-    cls.forward = _device_forward
-    _combinators[cls] = spec
-    return cls
+    unique across all four kinds (leaves, combinators, warps and shaders)."""
+    return _register("combinator", cls, params=params, hip=hip, cost=cost, children=children)
 
 
 def combinator_spec(node):
     """The combinator registration of this module's class (or of the registered class it derives from), or None."""
-    c = _registered_class(type(node), _combinators)
-    return None if c is None else _combinators[c]
+    return user_spec(node, "combinator")
 
 
 def combinator_children(node, spec: UserCombinator):
@@ -388,52 +383,14 @@ def register_warp(cls, *, params=(), hip: str, cost: int = 10, child: str = "sdf
     the source has the ``out`` pair, and a ``forward(self, query_coords)`` that composes them around the child.  Registration
     installs the same dispatch as ``register_leaf``: CUDA points go to the HIP evaluator, anything else to the class's own
     forward (kept under ``_rm_torch_forward``).  Registering a class again with the same source is a no-op; with other source,
-    parameters, cost or child attribute it is an error.  Identifiers are unique across leaves, combinators and warps."""
-    if not (isinstance(cls, type) and issubclass(cls, nn.Module)):
-        raise TypeError(f"register_warp: {cls!r} is not an nn.Module subclass")
-    if getattr(cls, "_rm_kind", None) is not None:
-        raise TypeError(f"register_warp: {cls.__name__} is already a ray_marching_amd node")
-    if _registered_class(cls) is not None:
-        raise TypeError(f"register_warp: {cls.__name__} is already registered as a leaf")
-    if _registered_class(cls, _combinators) is not None:
-        raise TypeError(f"register_warp: {cls.__name__} is already registered as a combinator")
-    if _registered_class(cls, _shaders) is not None:
-        raise TypeError(f"register_warp: {cls.__name__} is already registered as a shader")
-    if not callable(getattr(cls, "warp", None)):
-        raise TypeError(f"register_warp: {cls.__name__} has no warp(points [..., 3]) -> [..., 3] method")
-    if not isinstance(child, str) or not child:
-        raise ValueError("register_warp: child must name the attribute that holds the child module")
-    params = tuple(params)
-    if not all(isinstance(p, str) for p in params) or len(set(params)) != len(params):
-        raise ValueError("register_warp: params must be distinct attribute names")
-    name, has_out = _warp_identifier(hip)
-    if has_out != callable(getattr(cls, "out", None)):
-        raise TypeError(f"register_warp: {cls.__name__} " + (
-            f"has no out(values, points) method, but its source defines {name}_out_fwd / {name}_out_vjp" if has_out else
-            f"has an out(values, points) method, but its source defines no {name}_out_fwd / {name}_out_vjp"))
-    spec = UserWarp(cls, name, params, hip, int(cost), hashlib.sha1(hip.encode()).hexdigest(), child, has_out,
-                    _has_bound(hip, name, "warp"))
-    if spec.cost < 0:
-        raise ValueError("register_warp: cost must be >= 0")
-    old = _warps.get(cls)
-    if old is not None:
-        if (old.sha1, old.params, old.cost, old.child) != (spec.sha1, spec.params, spec.cost, spec.child):
-            raise ValueError(f"register_warp: {cls.__name__} is already registered with different source, parameters, cost or "
-                             "child attribute")
-        return cls
-    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()) + list(_shaders.values()):
-        if other.name == spec.name:
-            raise ValueError(f"register_warp: the identifier {spec.name!r} is already used by {other.cls.__name__}")
-    cls._rm_torch_forward = _torch_forward(cls)
-    cls.forward = _device_forward
-    _warps[cls] = spec
-    return cls
+    parameters, cost or child attribute it is an error.  Identifiers are unique across all four kinds (leaves, combinators,
+    warps and shaders)."""
+    return _register("warp", cls, params=params, hip=hip, cost=cost, child=child)
 
 
 def warp_spec(node):
     """The warp registration of this module's class (or of the registered class it derives from), or None."""
-    c = _registered_class(type(node), _warps)
-    return None if c is None else _warps[c]
+    return user_spec(node, "warp")
 
 
 def warp_child(node, spec: UserWarp):
@@ -454,38 +411,13 @@ def register_shader(cls, *, params=(), hip: str):
     ``cls`` has ``forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals) -> [..., 3]``,
     the first six arguments of the reference's ``Shader.forward`` (``camera_orientation`` [N,4], ``pixel_frames`` [N,3,3]); it is
     the CPU statement of the shader and is NOT replaced.  Registering a class again with the same source is a no-op; with other
-    source or parameters it is an error.  Identifiers are unique across leaves, combinators, warps and shaders."""
-    if not (isinstance(cls, type) and issubclass(cls, nn.Module)):
-        raise TypeError(f"register_shader: {cls!r} is not an nn.Module subclass")
-    if getattr(cls, "_rm_kind", None) is not None:
-        raise TypeError(f"register_shader: {cls.__name__} is already a ray_marching_amd node")
-    for registry, what in ((_registry, "leaf"), (_combinators, "combinator"), (_warps, "warp")):
-        if _registered_class(cls, registry) is not None:
-            raise TypeError(f"register_shader: {cls.__name__} is already registered as a {what}")
-    if cls.forward is nn.Module.forward:
-        raise TypeError(f"register_shader: {cls.__name__} has no forward(px_coords, camera_orientation, pixel_frames, ray_directions, "
-                        "surface_coords, surface_normals)")
-    params = tuple(params)
-    if not all(isinstance(p, str) for p in params) or len(set(params)) != len(params):
-        raise ValueError("register_shader: params must be distinct attribute names")
-    name = _shader_identifier(hip)
-    spec = UserShader(cls, name, params, hip, hashlib.sha1(hip.encode()).hexdigest())
-    old = _shaders.get(cls)
-    if old is not None:
-        if (old.sha1, old.params) != (spec.sha1, spec.params):
-            raise ValueError(f"register_shader: {cls.__name__} is already registered with different source or parameters")
-        return cls
-    for other in list(_registry.values()) + list(_combinators.values()) + list(_warps.values()) + list(_shaders.values()):
-        if other.name == spec.name:          # (a scene's user types and the shader are compiled into one translation unit)
-            raise ValueError(f"register_shader: the identifier {spec.name!r} is already used by {other.cls.__name__}")
-    _shaders[cls] = spec
-    return cls
+    source or parameters it is an error.  Identifiers are unique across all four kinds (leaves, combinators, warps and shaders)."""
+    return _register("shader", cls, params=params, hip=hip)
 
 
 def shader_spec(node):
     """The shader registration of this module's class (or of the registered class it derives from), or None."""
-    c = _registered_class(type(node), _shaders)
-    return None if c is None else _shaders[c]
+    return user_spec(node, "shader")
 
 
 def shader_parameters(shader, spec: UserShader):

@@ -92,26 +92,32 @@ def scene_hash(cs: CompiledScene, precision: str = "exact") -> str:
     return hashlib.sha1((repr(cs.signature) + sources_hash() + tag).encode()).hexdigest()[:16]
 
 
+_NAN = '__builtin_nanf("")'
+
+
+def _dispatcher(prototype: str, cases, default: str = "break;", after: str = "") -> str:
+    """A device function that switches over the user type: ``cases`` are (type, statements) pairs, ``after`` follows the switch."""
+    return (prototype + " {\n  switch (type) {\n" + "".join(f"    case {t}: {body}\n" for t, body in cases)
+            + f"    default: {default}\n  }}\n{after}}}\n")
+
+
 def _leaf_section(cs: CompiledScene) -> str:
     """User leaf sources and the dispatch over the leaf type (RM_OP_USER: aux0), for the header's first inclusion from
     inside namespace rm (csrc/rm_device.h); user_leaf_bound calls the NAME_bound of the types that bring one."""
-    cases_f = "".join(f"    case {t}: return {name}_fwd<Fast>(p, theta);\n" for t, (name, _, _) in enumerate(cs.user_leaves))
-    cases_v = "".join(f"    case {t}: {name}_vjp<Fast>(p, theta, g, gp, gtheta); break;\n" for t, (name, _, _) in enumerate(cs.user_leaves))
-    cases_b = "".join(f"    case {t}: {name}_bound(theta, b); break;\n"
-                      for t, ((name, _, _), bounded) in enumerate(zip(cs.user_leaves, cs.user_bounded)) if bounded)
+    names = [(t, name) for t, (name, _, _) in enumerate(cs.user_leaves)]
     sources = "".join(f"// user leaf {t}: {name}, {n} parameter floats, sha1 {sha}\n{src.strip()}\n"
                       for t, ((name, n, sha), src) in enumerate(zip(cs.user_leaves, cs.user_sources)))
     return (
         f"#define RM_USER_LEAVES {len(cs.user_leaves)}\n"
         f"#define RM_USER_MAX_PARAMS {max(1, max(n for _, n, _ in cs.user_leaves))}\n"
-        + sources +
-        "template <bool Fast> RM_DEV float user_leaf_fwd(int type, V3 p, const float* theta) {\n"
-        "  switch (type) {\n" + cases_f + "    default: return __builtin_nanf(\"\");\n  }\n}\n"
-        "template <bool Fast> RM_DEV void user_leaf_vjp(int type, V3 p, const float* theta, float g, V3& gp, float* gtheta) {\n"
-        "  switch (type) {\n" + cases_v + "    default: break;\n  }\n}\n"
+        + sources
+        + _dispatcher("template <bool Fast> RM_DEV float user_leaf_fwd(int type, V3 p, const float* theta)",
+                      [(t, f"return {name}_fwd<Fast>(p, theta);") for t, name in names], f"return {_NAN};")
+        + _dispatcher("template <bool Fast> RM_DEV void user_leaf_vjp(int type, V3 p, const float* theta, float g, V3& gp, float* gtheta)",
+                      [(t, f"{name}_vjp<Fast>(p, theta, g, gp, gtheta); break;") for t, name in names])
         # (leaf types without a NAME_bound leave `b` as it arrives: nothing known)
-        "RM_DEV void user_leaf_bound(int type, const float* theta, LeafBound& b) {\n"
-        "  switch (type) {\n" + cases_b + "    default: break;\n  }\n}\n")
+        + _dispatcher("RM_DEV void user_leaf_bound(int type, const float* theta, LeafBound& b)",
+                      [(t, f"{name}_bound(theta, b); break;") for t, name in names if cs.user_bounded[t]]))
 
 
 def _combinator_section(cs: CompiledScene) -> str:
@@ -119,22 +125,20 @@ def _combinator_section(cs: CompiledScene) -> str:
     inclusion as the leaf section and independent of it.  A type is a (class, children) pair; the caller's N selects, at
     compile time, the one instantiation of NAME_fwd / NAME_vjp a case can mean."""
     types = cs.user_combinators
-    cases_f = "".join(f"    case {t}: if constexpr (N == {n}) return {name}_fwd<Fast, {n}>(d, theta); break;\n"
-                      for t, (name, n, _, _) in enumerate(types))
-    cases_v = "".join(f"    case {t}: if constexpr (N == {n}) {name}_vjp<Fast, {n}>(d, theta, g, gd, gtheta); break;\n"
-                      for t, (name, n, _, _) in enumerate(types))
     listing = "".join(f"// user combinator type {t}: {name}, {n} children, {floats} parameter floats, sha1 {sha}\n"
                       for t, (name, n, floats, sha) in enumerate(types))
     sources = "".join(src.strip() + "\n" for src in cs.user_combinator_sources)
     return (
         f"#define RM_USER_COMBINATORS {len(types)}\n"
         f"#define RM_USER_COMB_MAX_PARAMS {max(1, max(floats for _, _, floats, _ in types))}\n"
-        + listing + sources +
-        "template <bool Fast, int N> RM_DEV float user_comb_fwd(int type, const float (&d)[N], const float* theta) {\n"
-        "  switch (type) {\n" + cases_f + "    default: break;\n  }\n  return __builtin_nanf(\"\");\n}\n"
-        "template <bool Fast, int N> RM_DEV void user_comb_vjp(int type, const float (&d)[N], const float* theta, float g, "
-        "float (&gd)[N], float* gtheta) {\n"
-        "  switch (type) {\n" + cases_v + "    default: break;\n  }\n}\n")
+        + listing + sources
+        + _dispatcher("template <bool Fast, int N> RM_DEV float user_comb_fwd(int type, const float (&d)[N], const float* theta)",
+                      [(t, f"if constexpr (N == {n}) return {name}_fwd<Fast, {n}>(d, theta); break;") for t, (name, n, _, _) in enumerate(types)],
+                      after=f"  return {_NAN};\n")
+        + _dispatcher("template <bool Fast, int N> RM_DEV void user_comb_vjp(int type, const float (&d)[N], const float* theta, float g, "
+                      "float (&gd)[N], float* gtheta)",
+                      [(t, f"if constexpr (N == {n}) {name}_vjp<Fast, {n}>(d, theta, g, gd, gtheta); break;")
+                       for t, (name, n, _, _) in enumerate(types)]))
 
 
 def _warp_section(cs: CompiledScene) -> str:
@@ -142,33 +146,27 @@ def _warp_section(cs: CompiledScene) -> str:
     the leaf and combinator sections and independent of both.  The `out` switches list the types that bring one, and so does
     user_warp_bound, which exists (with RM_USER_WARP_BOUNDS) only where at least one type brings a NAME_bound."""
     types = cs.user_warps
-    cases_f = "".join(f"    case {t}: return {name}_fwd<Fast>(p, theta);\n" for t, (name, _, _, _) in enumerate(types))
-    cases_v = "".join(f"    case {t}: {name}_vjp<Fast>(p, theta, gq, gp, gtheta); break;\n" for t, (name, _, _, _) in enumerate(types))
-    cases_of = "".join(f"    case {t}: return {name}_out_fwd<Fast>(d, p, theta);\n" for t, (name, _, out, _) in enumerate(types) if out)
-    cases_ov = "".join(f"    case {t}: {name}_out_vjp<Fast>(d, p, theta, g, gd, gp, gtheta); break;\n"
-                       for t, (name, _, out, _) in enumerate(types) if out)
+    names = [(t, name) for t, (name, _, _, _) in enumerate(types)]
+    with_out = [(t, name) for t, name in names if types[t][2]]
     sources = "".join(f"// user warp {t}: {name}, {n} parameter floats, {'with' if out else 'no'} out, sha1 {sha}\n{src.strip()}\n"
                       for t, ((name, n, out, sha), src) in enumerate(zip(types, cs.user_warp_sources)))
     # (only where a type brings NAME_bound: every other scene keeps the header, hence the library, it always had)
-    cases_b = "".join(f"    case {t}: {name}_bound(theta, b); return true;\n"
-                      for t, ((name, _, _, _), bounded) in enumerate(zip(types, cs.user_warp_bounded)) if bounded)
-    bound = "" if not cases_b else (
-        "#define RM_USER_WARP_BOUNDS 1\n"
-        "RM_DEV bool user_warp_bound(int type, const float* theta, LeafBound& b) {\n"
-        "  switch (type) {\n" + cases_b + "    default: return false;\n  }\n}\n")
+    bounded = [(t, f"{name}_bound(theta, b); return true;") for t, name in names if cs.user_warp_bounded[t]]
+    bound = "" if not bounded else "#define RM_USER_WARP_BOUNDS 1\n" + _dispatcher(
+        "RM_DEV bool user_warp_bound(int type, const float* theta, LeafBound& b)", bounded, "return false;")
     return (
         f"#define RM_USER_WARPS {len(types)}\n"
         f"#define RM_USER_WARP_MAX_PARAMS {max(1, max(n for _, n, _, _ in types))}\n"
-        + sources +
-        "template <bool Fast> RM_DEV V3 user_warp_fwd(int type, V3 p, const float* theta) {\n"
-        "  switch (type) {\n" + cases_f + "    default: return mk3(__builtin_nanf(\"\"), __builtin_nanf(\"\"), __builtin_nanf(\"\"));\n  }\n}\n"
-        "template <bool Fast> RM_DEV void user_warp_vjp(int type, V3 p, const float* theta, V3 gq, V3& gp, float* gtheta) {\n"
-        "  switch (type) {\n" + cases_v + "    default: break;\n  }\n}\n"
-        "template <bool Fast> RM_DEV float user_warp_out_fwd(int type, float d, V3 p, const float* theta) {\n"
-        "  switch (type) {\n" + cases_of + "    default: return __builtin_nanf(\"\");\n  }\n}\n"
-        "template <bool Fast> RM_DEV void user_warp_out_vjp(int type, float d, V3 p, const float* theta, float g, float& gd, V3& gp, "
-        "float* gtheta) {\n"
-        "  switch (type) {\n" + cases_ov + "    default: break;\n  }\n}\n"
+        + sources
+        + _dispatcher("template <bool Fast> RM_DEV V3 user_warp_fwd(int type, V3 p, const float* theta)",
+                      [(t, f"return {name}_fwd<Fast>(p, theta);") for t, name in names], f"return mk3({_NAN}, {_NAN}, {_NAN});")
+        + _dispatcher("template <bool Fast> RM_DEV void user_warp_vjp(int type, V3 p, const float* theta, V3 gq, V3& gp, float* gtheta)",
+                      [(t, f"{name}_vjp<Fast>(p, theta, gq, gp, gtheta); break;") for t, name in names])
+        + _dispatcher("template <bool Fast> RM_DEV float user_warp_out_fwd(int type, float d, V3 p, const float* theta)",
+                      [(t, f"return {name}_out_fwd<Fast>(d, p, theta);") for t, name in with_out], f"return {_NAN};")
+        + _dispatcher("template <bool Fast> RM_DEV void user_warp_out_vjp(int type, float d, V3 p, const float* theta, float g, float& gd, "
+                      "V3& gp, float* gtheta)",
+                      [(t, f"{name}_out_vjp<Fast>(d, p, theta, g, gd, gp, gtheta); break;") for t, name in with_out])
         + bound)
 
 
@@ -213,7 +211,7 @@ def code_header(cs: CompiledScene) -> str:
     # warps only), by csrc/rm_kernels.h behind ShadeIn / ShadeGrad (RM_STATIC_CODE_LEAVES and RM_STATIC_CODE_SHADER: the user
     # shader only), then by csrc/rm_abi.hip for the program
     head = "// generated by ray_marching_amd/specialize.py -- scene program as a compile-time constant\n"
-    if not cs.user_leaves and not cs.user_combinators and not cs.user_warps and not cs.user_shader:
+    if not cs.has_user_types:
         return head + "#ifndef RM_STATIC_CODE_LEAVES\n" + program + "#endif\n"
     user = ((_leaf_section(cs) if cs.user_leaves else "") + (_combinator_section(cs) if cs.user_combinators else "")
             + (_warp_section(cs) if cs.user_warps else ""))
@@ -270,7 +268,7 @@ def build(cs: CompiledScene, force: bool = False, precision: str = "exact") -> s
     if not static_backward(cs):
         cmd.append("-DRM_NO_BACKWARD")
     cmd += [os.path.join(CSRC, "rm_abi.hip"), "-o", tmp]
-    if not cs.user_leaves and not cs.user_combinators and not cs.user_warps and not cs.user_shader:
+    if not cs.has_user_types:
         subprocess.run(cmd, check=True, cwd=CSRC)
     else:
         # user source goes through the compiler here: its diagnostics belong in the exception, and the frame kernel's
@@ -313,6 +311,14 @@ def _background_build(cs: CompiledScene, h: str):
             _builder["hash"] = None
 
 
+def _open(cs: CompiledScene, precision: str, h: str, path: str):
+    """The tail of load and load_user: build the library where it is missing, load it and remember it."""
+    if not os.path.isfile(path):
+        build(cs, precision=precision)
+    lib = _loaded[h] = _abi.bind(C.CDLL(path))
+    return lib
+
+
 def load(cs: CompiledScene, precision: str = "exact"):
     """The specialised library for this program, or None (policy in the module docstring)."""
     policy = os.environ.get("RM_SPECIALIZE", "auto")
@@ -322,14 +328,10 @@ def load(cs: CompiledScene, precision: str = "exact"):
     if h in _loaded:
         return _loaded[h]
     path = lib_path(cs, precision)
-    if not os.path.isfile(path):
-        if policy != "jit":
-            _loaded[h] = None
-            return None
-        build(cs, precision=precision)
-    lib = _abi.bind(C.CDLL(path))
-    _loaded[h] = lib
-    return lib
+    if not os.path.isfile(path) and policy != "jit":
+        _loaded[h] = None
+        return None
+    return _open(cs, precision, h, path)
 
 
 def load_user(cs: CompiledScene, precision: str = "exact"):
@@ -352,10 +354,7 @@ def load_user(cs: CompiledScene, precision: str = "exact"):
         if shutil.which(_hipcc()) is None:
             raise _abi.RmError(f"the specialised library {path} of a scene with user-defined {what} ({names}) is missing and "
                                "hipcc is not available to build it")
-        build(cs, precision=precision)
-    lib = _abi.bind(C.CDLL(path))
-    _loaded[h] = lib
-    return lib
+    return _open(cs, precision, h, path)
 
 
 def note_interpreted_launch(cs: CompiledScene):

@@ -1,4 +1,5 @@
 """Shared test helpers: oracle spec <-> product module conversion, fixtures, tolerances."""
+import contextlib
 import os
 
 import numpy as np
@@ -13,6 +14,32 @@ EPS = 5e-2
 
 def gold(name):
     return np.load(os.path.join(GOLD, name))
+
+
+@contextlib.contextmanager
+def environment(**env):
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _same(a, b):
+    return torch.equal(torch.nan_to_num(a, nan=-7.0), torch.nan_to_num(b, nan=-7.0)) and torch.equal(a.isnan(), b.isnan())
+
+
+def _points(n=4096, seed=0, lo=-2.5, hi=2.5):
+    return torch.rand(n, 3, generator=torch.Generator().manual_seed(seed)) * (hi - lo) + lo
+
+
+def _pose(z, dev="cuda"):
+    return torch.tensor([[1.0, 0.0, 0.0, 0.0]], device=dev), torch.tensor([[0.0, 0.0, z]], device=dev)
 
 
 def spec_to_module(spec):

@@ -6,7 +6,6 @@ culling on and off around them, and through a captured training loop.
 The CPU side of every GPU comparison is `cpu_eval()` below: ``combine`` of the combinator instance over the oracle's
 evaluation (oracle.sdf_oracle.sdf_eval) of its children, the way tests/test_user_leaf.py::composition does for the link.
 """
-import contextlib
 import os
 import warnings
 
@@ -17,6 +16,7 @@ import torch.nn as nn
 
 from oracle import sdf_oracle as O
 from tests import helpers as H
+from tests.helpers import _points, _pose, _same, environment
 
 DEV = "cuda"
 
@@ -215,20 +215,6 @@ def cpu_grad_spec(spec):
     return O.map_spec(spec, lambda x: x.clone().requires_grad_(True))
 
 
-@contextlib.contextmanager
-def environment(**env):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def gpu_test_programs():
     """Every test-defined program the GPU legs launch: the CPU suite and build() compile their libraries, so that a GPU run of
     the same tree finds them; where they are missing the library builds itself on first use."""
@@ -240,14 +226,6 @@ def gpu_test_programs():
         with environment(**env):
             out.append(compile_scene(nested_scene()))
     return list({specialize.scene_hash(cs): cs for cs in out}.values())
-
-
-def _same(a, b):
-    return torch.equal(torch.nan_to_num(a, nan=-7.0), torch.nan_to_num(b, nan=-7.0)) and torch.equal(a.isnan(), b.isnan())
-
-
-def _points(n=4096, seed=0, lo=-2.5, hi=2.5):
-    return torch.rand(n, 3, generator=torch.Generator().manual_seed(seed)) * (hi - lo) + lo
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -528,10 +506,6 @@ def test_specialised_library_cross_compiles_and_reports_its_combinators(monkeypa
 # --------------------------------------------------------------------------------------------------------------
 # GPU
 # --------------------------------------------------------------------------------------------------------------
-def _pose(z, dev=DEV):
-    return torch.tensor([[1.0, 0.0, 0.0, 0.0]], device=dev), torch.tensor([[0.0, 0.0, z]], device=dev)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("which", ["scene2", "closed_scene1"])
 def test_restated_union_is_bit_identical_with_the_builtin(which, monkeypatch):

@@ -7,7 +7,6 @@ built-in part and the leaf's own forward at the affine-transformed point.  test_
 pins that composition, bit for bit, to the same SDFLink instance inside the reference's own SDFUnion /
 SDFAffineTransformation.
 """
-import contextlib
 import os
 import warnings
 
@@ -18,6 +17,7 @@ import torch.nn as nn
 
 from oracle import ref_bridge, sdf_oracle as O
 from tests import helpers as H
+from tests.helpers import _points, _pose, _same, environment
 
 DEV = "cuda"
 
@@ -195,20 +195,6 @@ CULL_ENVS = {"siblings": [dict(RM_CULL_MIN_COST="0", RM_CULL="0"), dict(RM_CULL_
 CULL_SCENES = {"siblings": link_among_cullable_siblings, "blob": link_inside_a_blob, "tight_neighbour": link_with_a_tight_neighbour}
 
 
-@contextlib.contextmanager
-def environment(**env):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def gpu_test_programs():
     """Every test-defined program the GPU legs launch (the JIT leg's excepted): the CPU suite builds their libraries,
     so that a GPU run of the same tree finds them; where they are missing the library builds itself on first use."""
@@ -221,14 +207,6 @@ def gpu_test_programs():
                 out.append(compile_scene(CULL_SCENES[name]()))
     from ray_marching_amd import specialize
     return list({specialize.scene_hash(cs): cs for cs in out}.values())      # (the blob's default program is its RM_CULL=0 one)
-
-
-def _same(a, b):
-    return torch.equal(torch.nan_to_num(a, nan=-7.0), torch.nan_to_num(b, nan=-7.0)) and torch.equal(a.isnan(), b.isnan())
-
-
-def _points(n=4096, seed=0, lo=-2.5, hi=2.5):
-    return torch.rand(n, 3, generator=torch.Generator().manual_seed(seed)) * (hi - lo) + lo
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -407,10 +385,6 @@ def test_link_in_the_reference_combinators():
 # --------------------------------------------------------------------------------------------------------------
 # GPU
 # --------------------------------------------------------------------------------------------------------------
-def _pose(z, dev=DEV):
-    return torch.tensor([[1.0, 0.0, 0.0, 0.0]], device=dev), torch.tensor([[0.0, 0.0, z]], device=dev)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("which", ["scene2", "closed_scene1"])
 def test_restated_sphere_is_bit_identical_with_the_builtin(which, monkeypatch):

@@ -17,8 +17,8 @@ import torch
 import torch.nn as nn
 
 from tests import helpers as H
-from tests.test_user_leaf import (LINK, LINK_Q, LINK_T, TIGHT_END, _points, _pose, _same, closed_scene_with, environment,
-                                  scene2_with)
+from tests.helpers import _points, _pose, _same, environment
+from tests.test_user_leaf import LINK, LINK_Q, LINK_T, TIGHT_END, closed_scene_with, scene2_with
 
 DEV = "cuda"
 IDENT = [1.0, 0.0, 0.0, 0.0]

@@ -26,6 +26,7 @@ import torch.nn as nn
 
 from oracle import sdf_oracle as O
 from tests import helpers as H
+from tests.helpers import _same
 
 DEV = "cuda"
 
@@ -208,10 +209,6 @@ def _edit(shader):
     with torch.no_grad():
         first.mul_(0.5)
     last.data = (last.detach() * 1.5 + 0.05).clone()
-
-
-def _same(a, b):
-    return torch.equal(torch.nan_to_num(a, nan=-7.0), torch.nan_to_num(b, nan=-7.0)) and torch.equal(a.isnan(), b.isnan())
 
 
 # --------------------------------------------------------------------------------------------------------------

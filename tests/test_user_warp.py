@@ -9,7 +9,6 @@ tree: the oracle's functions (oracle.sdf_oracle) for the built-in nodes, ``warp`
 the user-defined ones.  Helpers, the restated-math mode of the oracle and every tolerance are those of
 tests/test_user_combinator.py.
 """
-import contextlib
 import copy
 import os
 import warnings
@@ -21,6 +20,7 @@ import torch.nn as nn
 
 from oracle import sdf_oracle as O
 from tests import helpers as H
+from tests.helpers import _points, _pose, _same, environment
 
 DEV = "cuda"
 
@@ -300,20 +300,6 @@ def cpu_parameters(spec):
     return own + [x for c in (kids if isinstance(kids, list) else [kids]) for x in cpu_parameters(c)]
 
 
-@contextlib.contextmanager
-def environment(**env):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def compiled_under(scene, env):
     """The scene compiled under ``env`` (compiler.compiled_for keeps the program with the module)."""
     from ray_marching_amd.compiler import compiled_for
@@ -339,14 +325,6 @@ def gpu_test_programs():
             with environment(**env):
                 out.append(compile_scene(CULL_SCENES[case]()))
     return list({specialize.scene_hash(cs): cs for cs in out}.values())
-
-
-def _same(a, b):
-    return torch.equal(torch.nan_to_num(a, nan=-7.0), torch.nan_to_num(b, nan=-7.0)) and torch.equal(a.isnan(), b.isnan())
-
-
-def _points(n=4096, seed=0, lo=-2.5, hi=2.5):
-    return torch.rand(n, 3, generator=torch.Generator().manual_seed(seed)) * (hi - lo) + lo
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -735,10 +713,6 @@ def test_specialised_library_cross_compiles_and_reports_its_warps(monkeypatch, t
 # --------------------------------------------------------------------------------------------------------------
 # GPU
 # --------------------------------------------------------------------------------------------------------------
-def _pose(z, dev=DEV):
-    return torch.tensor([[1.0, 0.0, 0.0, 0.0]], device=dev), torch.tensor([[0.0, 0.0, z]], device=dev)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("which", ["scene2", "closed_scene1", "scene2_placed"])
 def test_restated_affine_is_bit_identical_with_the_builtin(which, monkeypatch):

@@ -23,8 +23,9 @@ import torch
 import torch.nn as nn
 
 from tests import helpers as H
+from tests.helpers import _points, _pose, _same
 from tests.test_user_leaf_bounds import CULL_OFF, _compile, _on_device
-from tests.test_user_warp import IDENT, Q_ROT, TIGHT_END, UAFFINE_HIP, UAffine, _Unary, _points, _pose, _same, scene2_placed
+from tests.test_user_warp import IDENT, Q_ROT, TIGHT_END, UAFFINE_HIP, UAffine, _Unary, scene2_placed
 
 DEV = "cuda"
 
