@@ -113,6 +113,7 @@ class CompiledScene:
     user_warp_bounded: tuple = ()       # ... and whether each source brings a NAME_bound (the node's bound from its child's)
     user_shader: tuple = ()             # (identifier, parameter floats, sha1) of the user shader of a (scene, shader) program, else ()
     user_shader_source: str = ""        # its HIP source text
+    user_shader_probes: int = 0         # K: the scene probes it asks for per pixel (register_shader(probes=K)); 0: none
     shader_offset: int = 0              # where its theta starts in the block (= the scene's own n_params)
     _device_programs: dict = field(default_factory=dict)
     _table: dict = field(default_factory=dict)
@@ -481,7 +482,7 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
         offsets.append(cursor)
         table[id(p)] = cursor
         cursor += p.numel()
-    shader_offset, user_shader, shader_source = cursor, (), ""
+    shader_offset, user_shader, shader_source, shader_probes = cursor, (), "", 0
     if shader is not None:
         spec = shader_spec(shader)
         if spec is None:
@@ -493,7 +494,7 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
             leaves.append(p)
             offsets.append(cursor)
             cursor += p.numel()
-        user_shader, shader_source = (spec.name, cursor - shader_offset, spec.sha1), spec.hip
+        user_shader, shader_source, shader_probes = (spec.name, cursor - shader_offset, spec.sha1), spec.hip, spec.probes
     n_params = cursor                 # (derived constants start behind the shader's floats)
     em = _Emitter(table)
     # derived block = [capsule constants of every SDFLine (gradients flow through them) | cull bounds, bound tables]
@@ -514,6 +515,8 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
     slots = [user_leaves, user_combinators, user_warps, user_shader]
     while slots and not slots[-1]:
         slots.pop()
+    if shader_probes:                 # (the same source registered with another K is another header; K = 0 adds nothing)
+        slots.append(("probes", shader_probes))
     signature = (tuple(map(tuple, program.tolist())), n_params, em.n_derived, em.max_depth, em.n_slots, em.n_grad_derived, *slots)
     return CompiledScene(program=program, leaves=leaves, leaf_names=names, leaf_offsets=offsets,
                          n_params=n_params, n_derived=em.n_derived, n_grad_derived=em.n_grad_derived, stack_floats=em.max_depth,
@@ -523,7 +526,8 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
                          user_combinator_sources=tuple({u.name: u.hip for u, _, _ in comb_types}.values()),
                          user_warps=user_warps, user_warp_sources=tuple(u.hip for u, _ in warp_types),
                          user_warp_bounded=tuple(u.bounded for u, _ in warp_types),
-                         user_shader=user_shader, user_shader_source=shader_source, shader_offset=shader_offset)
+                         user_shader=user_shader, user_shader_source=shader_source, shader_offset=shader_offset,
+                         user_shader_probes=shader_probes)
 
 
 def structure_key(module: nn.Module):

@@ -563,3 +563,222 @@ template <bool Fast> RM_DEV void depth_cue_vjp(const rm::ShadeIn& s, const float
 """
 
 register_shader(DepthCueShader, params=("density", "far_colour"), hip=_DEPTH_CUE_HIP)
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# Shaders that probe the scene (register_shader(probes=K)): K more distance evaluations around the hit point
+# --------------------------------------------------------------------------------------------------------------------
+class AmbientOcclusionShader(nn.Module):
+    """Fixed-height ambient occlusion on a Lambertian term: five probes at ``p + h_k n``, ``h_k = reach (k+1)/5``; where the
+    scene is nearer than the height says, something occludes: ``occ = sum_k 2^-k max(h_k - d_k, 0) / reach`` and
+    ``rgb = albedo * clamp(-(v . n), 0, 1) / (1 + strength * occ)``.  Five parameter floats (``reach``, ``strength``, ``albedo``
+    [3]); the probe positions depend on the surface point, the normal and ``reach``.  No transcendental function.
+
+    ``scene``: a callable ``points[..., 3] -> [..., 1]`` (an SDF module, or the frame kernels' scene on the GPU)."""
+
+    def __init__(self, reach: float = 0.4, strength: float = 2.0, albedo=(1.0, 1.0, 1.0)) -> None:
+        super().__init__()
+        self.reach = nn.Parameter(torch.tensor(reach, dtype=torch.float32))
+        self.strength = nn.Parameter(torch.tensor(strength, dtype=torch.float32))
+        self.albedo = nn.Parameter(torch.tensor(albedo, dtype=torch.float32))
+
+    def forward(self, px_coords: Tensor, camera_orientation: Tensor, pixel_frames: Tensor, ray_directions: Tensor,
+                surface_coords: Tensor, surface_normals: Tensor, scene) -> Tensor:
+        occ = 0.0
+        for k in range(5):
+            h = self.reach * ((k + 1) / 5)
+            d = scene(surface_coords + h * surface_normals)
+            occ = occ + (h - d).clamp(min=0) * (2.0 ** -k) / self.reach
+        c = (ray_directions * surface_normals).sum(dim=-1, keepdim=True).neg().clamp(0, 1)
+        return self.albedo * (c / (self.strength * occ + 1))
+
+
+# theta = {reach, strength, albedo[3]}; the forward restates the ATen op stream above (mul().sum(-1): dot_seq, clamp: t_clamp,
+# every product and sum rounded on its own), the VJPs are autograd's, written out.  k is a run-time value in the probe pair
+# (the kernels' probe loop is rolled) and a constant wherever d / gd are indexed (loops over the five probes are unrolled).
+_AMBIENT_OCCLUSION_HIP = r"""
+template <bool Fast> RM_DEV rm::V3 ambient_occlusion_probe(int k, const rm::ShadeIn& s, const float* theta) {
+  const float h = theta[0] * ((float)(k + 1) / 5.0f);
+  return mk3(s.p.x + h * s.n.x, s.p.y + h * s.n.y, s.p.z + h * s.n.z);
+}
+template <bool Fast> RM_DEV void ambient_occlusion_probe_vjp(int k, const rm::ShadeIn& s, const float* theta, rm::V3 gq, rm::ShadeGrad& gs,
+                                                             float* gtheta) {
+  const float ck = (float)(k + 1) / 5.0f;
+  const float h = theta[0] * ck;
+  gs.p = gs.p + gq;
+  gs.n = gs.n + h * gq;
+  gtheta[0] += dot_seq(gq, s.n) * ck;
+}
+template <bool Fast> RM_DEV rm::V3 ambient_occlusion_fwd(const rm::ShadeIn& s, const float* theta, const float* d) {
+  float occ = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const float h = theta[0] * ((float)(k + 1) / 5.0f);
+    occ = occ + (t_clamp(h - d[k], 0.0f, __builtin_inff()) * (1.0f / (float)(1 << k))) / theta[0];
+  }
+  const float c = t_clamp(-dot_seq(s.v, s.n), 0.0f, 1.0f);
+  const float shade = c / (theta[1] * occ + 1.0f);
+  return mk3(theta[2] * shade, theta[3] * shade, theta[4] * shade);
+}
+template <bool Fast> RM_DEV void ambient_occlusion_vjp(const rm::ShadeIn& s, const float* theta, const float* d, rm::V3 g, rm::ShadeGrad& gs,
+                                                       float* gtheta, float* gd) {
+  float occ = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const float h = theta[0] * ((float)(k + 1) / 5.0f);
+    occ = occ + div_t<Fast>(t_clamp(h - d[k], 0.0f, __builtin_inff()) * (1.0f / (float)(1 << k)), theta[0]);
+  }
+  const float e = -dot_seq(s.v, s.n);
+  const float c = t_clamp(e, 0.0f, 1.0f);
+  const float den = theta[1] * occ + 1.0f;
+  const float shade = div_t<Fast>(c, den);
+  gtheta[2] = g.x * shade; gtheta[3] = g.y * shade; gtheta[4] = g.z * shade;
+  const float gshade = (g.x * theta[2] + g.y * theta[3]) + g.z * theta[4];
+  const float gc = div_t<Fast>(gshade, den);
+  const float gden = -(gc * shade);                            // shade = c / den
+  gtheta[1] = gden * occ;
+  const float gocc = gden * theta[1];
+  const float ge = (e >= 0.0f && e <= 1.0f) ? gc : 0.0f;        // clamp passes the gradient on the closed interval
+  gs.v = gs.v - ge * s.n;
+  gs.n = gs.n - ge * s.v;
+  float greach = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const float ck = (float)(k + 1) / 5.0f, wk = 1.0f / (float)(1 << k);
+    const float x = theta[0] * ck - d[k];
+    const float term = div_t<Fast>(t_clamp(x, 0.0f, __builtin_inff()) * wk, theta[0]);
+    const float gm = (x >= 0.0f) ? div_t<Fast>(gocc * wk, theta[0]) : 0.0f;    // clamp(min=0) passes the gradient at 0
+    gd[k] = -gm;
+    greach += gm * ck - div_t<Fast>(gocc * term, theta[0]);
+  }
+  gtheta[0] = greach;
+}
+"""
+
+register_shader(AmbientOcclusionShader, params=("reach", "strength", "albedo"), hip=_AMBIENT_OCCLUSION_HIP, probes=5)
+
+
+class SoftShadowShader(nn.Module):
+    """A distant light with a fixed-step soft shadow: eight probes at ``p + bias n + t_k l``, ``t_k = reach (k+1)/8``, ``l`` the
+    normalised ``light_direction`` (as in DirectionalLightShader); ``shadow = min_k clamp(sharpness d_k / t_k, 0, 1)`` and
+    ``rgb = albedo * (ambient + (1 - ambient) * clamp(n . l, 0, 1) * shadow)``.  Nine trainable floats (``light_direction`` [3],
+    ``albedo`` [3], ``ambient``, ``sharpness``, ``reach``).
+
+    The gradient of the minimum goes to the one index that PyTorch's ``min(dim)`` reports, the first minimal one; ties occur
+    only between clamped values (0 or 1), whose gradient is zero on both sides, so which of them is picked does not matter.
+    ``bias`` is a constructor constant, not a trainable parameter: it is kept as a frozen ``nn.Parameter`` (``requires_grad =
+    False``) only so that its value travels in ``theta`` like the others; it receives no gradient.  The steps are fixed: a
+    marched shadow ray, whose next point depends on the last distance, is not what probes can say (extensions.py).
+
+    ``scene``: a callable ``points[..., 3] -> [..., 1]``."""
+
+    def __init__(self, light_direction=(0.0, 0.0, -1.0), albedo=(1.0, 1.0, 1.0), ambient: float = 0.15, sharpness: float = 8.0,
+                 reach: float = 1.5, bias: float = 0.02) -> None:
+        super().__init__()
+        self.light_direction = nn.Parameter(torch.tensor(light_direction, dtype=torch.float32))
+        self.albedo = nn.Parameter(torch.tensor(albedo, dtype=torch.float32))
+        self.ambient = nn.Parameter(torch.tensor(ambient, dtype=torch.float32))
+        self.sharpness = nn.Parameter(torch.tensor(sharpness, dtype=torch.float32))
+        self.reach = nn.Parameter(torch.tensor(reach, dtype=torch.float32))
+        self.bias = nn.Parameter(torch.tensor(bias, dtype=torch.float32), requires_grad=False)
+
+    def forward(self, px_coords: Tensor, camera_orientation: Tensor, pixel_frames: Tensor, ray_directions: Tensor,
+                surface_coords: Tensor, surface_normals: Tensor, scene) -> Tensor:
+        light = self.light_direction / torch.linalg.vector_norm(self.light_direction)
+        start = surface_coords + self.bias * surface_normals
+        steps = []
+        for k in range(8):
+            t = self.reach * ((k + 1) / 8)
+            steps.append((self.sharpness * scene(start + t * light) / t).clamp(0, 1))
+        shadow = torch.cat(steps, dim=-1).min(dim=-1, keepdim=True).values
+        c = (surface_normals * light).sum(dim=-1, keepdim=True).clamp(0, 1)
+        return self.albedo * (self.ambient + (1 - self.ambient) * c * shadow)
+
+
+# theta = {light_direction[3], albedo[3], ambient, sharpness, reach, bias}
+_SOFT_SHADOW_HIP = r"""
+template <bool Fast> RM_DEV rm::V3 soft_shadow_probe(int k, const rm::ShadeIn& s, const float* theta) {
+  const rm::V3 L = mk3(theta[0], theta[1], theta[2]);
+  const float ln = norm3(L);
+  const rm::V3 l = mk3(L.x / ln, L.y / ln, L.z / ln);
+  const float t = theta[8] * ((float)(k + 1) / 8.0f);
+  return mk3((s.p.x + theta[9] * s.n.x) + t * l.x, (s.p.y + theta[9] * s.n.y) + t * l.y, (s.p.z + theta[9] * s.n.z) + t * l.z);
+}
+template <bool Fast> RM_DEV void soft_shadow_probe_vjp(int k, const rm::ShadeIn& s, const float* theta, rm::V3 gq, rm::ShadeGrad& gs,
+                                                       float* gtheta) {
+  const rm::V3 L = mk3(theta[0], theta[1], theta[2]);
+  const float ln = norm3_t<Fast>(L);
+  const rm::V3 l = mk3(div_t<Fast>(L.x, ln), div_t<Fast>(L.y, ln), div_t<Fast>(L.z, ln));
+  const float ck = (float)(k + 1) / 8.0f;
+  const float t = theta[8] * ck;
+  gs.p = gs.p + gq;
+  gs.n = gs.n + theta[9] * gq;
+  gtheta[8] += dot_seq(gq, l) * ck;
+  // l = L / |L|: dL = (gl - l (gl . l)) / |L|, gl = t gq
+  const rm::V3 gl = t * gq;
+  const float gll = dot_seq(gl, l);
+  gtheta[0] += div_t<Fast>(gl.x - l.x * gll, ln);
+  gtheta[1] += div_t<Fast>(gl.y - l.y * gll, ln);
+  gtheta[2] += div_t<Fast>(gl.z - l.z * gll, ln);
+}
+template <bool Fast> RM_DEV rm::V3 soft_shadow_fwd(const rm::ShadeIn& s, const float* theta, const float* d) {
+  const rm::V3 L = mk3(theta[0], theta[1], theta[2]);
+  const float ln = norm3(L);
+  const rm::V3 l = mk3(L.x / ln, L.y / ln, L.z / ln);
+  float shadow = __builtin_inff();
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float t = theta[8] * ((float)(k + 1) / 8.0f);
+    shadow = fminf(shadow, t_clamp((theta[7] * d[k]) / t, 0.0f, 1.0f));
+  }
+  const float c = t_clamp(dot_seq(s.n, l), 0.0f, 1.0f);
+  const float k = theta[6] + ((1.0f - theta[6]) * c) * shadow;
+  return mk3(theta[3] * k, theta[4] * k, theta[5] * k);
+}
+template <bool Fast> RM_DEV void soft_shadow_vjp(const rm::ShadeIn& s, const float* theta, const float* d, rm::V3 g, rm::ShadeGrad& gs,
+                                                 float* gtheta, float* gd) {
+  const rm::V3 L = mk3(theta[0], theta[1], theta[2]);
+  const float ln = norm3_t<Fast>(L);
+  const rm::V3 l = mk3(div_t<Fast>(L.x, ln), div_t<Fast>(L.y, ln), div_t<Fast>(L.z, ln));
+  // the first minimal step, as min(dim) reports it: its index j, the unclamped value xj, its distance dj
+  float shadow = __builtin_inff(), xj = 0.0f, dj = 0.0f;
+  int j = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float x = div_t<Fast>(theta[7] * d[k], theta[8] * ((float)(k + 1) / 8.0f));
+    const float v = t_clamp(x, 0.0f, 1.0f);
+    const bool less = v < shadow;
+    j = less ? k : j; xj = less ? x : xj; dj = less ? d[k] : dj; shadow = less ? v : shadow;
+  }
+  const float dn = dot_seq(s.n, l);
+  const float c = t_clamp(dn, 0.0f, 1.0f);
+  const float lit = (1.0f - theta[6]) * c;
+  const float k = theta[6] + lit * shadow;
+  gtheta[3] = g.x * k; gtheta[4] = g.y * k; gtheta[5] = g.z * k;
+  const float gk = (g.x * theta[3] + g.y * theta[4]) + g.z * theta[5];
+  const float glit = gk * shadow, gshadow = gk * lit;
+  gtheta[6] = gk - glit * c;
+  const float gc = glit * (1.0f - theta[6]);
+  const float gdn = (dn >= 0.0f && dn <= 1.0f) ? gc : 0.0f;     // clamp passes the gradient on the closed interval
+  gs.n = gs.n + gdn * l;
+  const rm::V3 gl = gdn * s.n;
+  const float gll = dot_seq(gl, l);
+  gtheta[0] = div_t<Fast>(gl.x - l.x * gll, ln);
+  gtheta[1] = div_t<Fast>(gl.y - l.y * gll, ln);
+  gtheta[2] = div_t<Fast>(gl.z - l.z * gll, ln);
+  // shadow = clamp(xj, 0, 1), xj = sharpness dj / tj, tj = reach (j+1)/8
+  const float cj = (float)(j + 1) / 8.0f;
+  const float tj = theta[8] * cj;
+  const float gx = (xj >= 0.0f && xj <= 1.0f) ? gshadow : 0.0f;
+  const float gxt = div_t<Fast>(gx, tj);
+  gtheta[7] = gxt * dj;
+  gtheta[8] = -(gxt * xj) * cj;
+  gtheta[9] = 0.0f;                                              // bias: a constant (frozen), no gradient
+  const float gdj = gxt * theta[7];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) gd[k] = (k == j) ? gdj : 0.0f;
+}
+"""
+
+register_shader(SoftShadowShader, params=("light_direction", "albedo", "ambient", "sharpness", "reach", "bias"), hip=_SOFT_SHADOW_HIP,
+                probes=8)

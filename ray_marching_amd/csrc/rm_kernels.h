@@ -950,6 +950,15 @@ struct ShadeGrad {
 //     template <bool Fast> RM_DEV void   NAME_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 g, rm::ShadeGrad& gs, float* gtheta);
 // and user_shader_fwd / user_shader_vjp, which forward to them.  Without RM_USER_SHADER (the generic libraries, every
 // library of a scene alone) nothing of it exists.
+// A shader with scene probes (register_shader(probes=K), 1 <= K <= 8) adds
+//     #define RM_USER_SHADER_PROBES K,
+//     template <bool Fast> RM_DEV rm::V3 NAME_probe(int k, const rm::ShadeIn& s, const float* theta);
+//     template <bool Fast> RM_DEV void   NAME_probe_vjp(int k, const rm::ShadeIn& s, const float* theta, rm::V3 gq, rm::ShadeGrad& gs, float* gtheta);
+// (user_shader_probe / user_shader_probe_vjp forward to them), and its NAME_fwd / NAME_vjp take `const float* d`, the scene's
+// values at the K probe points, behind theta (the VJP also `float* gd` at its end).  Probe k is a function of ShadeIn and theta
+// alone, so both passes are flat loops over k; they stay rolled (one inlined copy of the scene evaluator each, like the taps'),
+// and d[] / gd[] are only ever indexed by constants (user_probe_push / user_probe_pop), so they stay registers.  Without
+// RM_USER_SHADER_PROBES nothing of it exists either.
 #ifdef RM_STATIC_CODE
 #define RM_STATIC_CODE_LEAVES
 #define RM_STATIC_CODE_SHADER
@@ -958,12 +967,49 @@ struct ShadeGrad {
 #undef RM_STATIC_CODE_LEAVES
 #endif
 
+#ifdef RM_USER_SHADER_PROBES
+// 1: the two probe loops stay rolled (the default, chosen from the compiler's resource remarks:
+// profiles/user_shader_probes_resource_usage.txt); -DRM_USER_PROBE_UNROLL=8 unrolls them fully (K inlined copies of the scene)
+#ifndef RM_USER_PROBE_UNROLL
+#define RM_USER_PROBE_UNROLL 1
+#endif
+// d[] and gd[] in a rolled loop over k without a run-time index (an array indexed at run time goes to scratch, and so does one
+// whose elements a select chain picks from: LLVM turns the chain back into an index).  Both rotate the array by one place
+// through constant indices instead: K pushes fill d[0..K-1] in order, K pops hand out gd[0], gd[1], ... in order.
+RM_DEV void user_probe_push(float (&d)[RM_USER_SHADER_PROBES], float v) {
+#pragma unroll
+  for (int j = 0; j + 1 < RM_USER_SHADER_PROBES; ++j) d[j] = d[j + 1];
+  d[RM_USER_SHADER_PROBES - 1] = v;
+}
+RM_DEV float user_probe_pop(float (&gd)[RM_USER_SHADER_PROBES]) {
+  const float v = gd[0];
+#pragma unroll
+  for (int j = 0; j + 1 < RM_USER_SHADER_PROBES; ++j) gd[j] = gd[j + 1];
+  return v;
+}
+// the scene at the K probe points of one pixel: the full evaluator, as for the taps (the carried cull decisions of eval_near
+// hold along the march only)
+template <class SceneT>
+RM_DEV void user_probe_values(const SceneT& scene, const ShadeIn& si, const float* theta, float (&d)[RM_USER_SHADER_PROBES]) {
+#pragma unroll RM_USER_PROBE_UNROLL
+  for (int k = 0; k < RM_USER_SHADER_PROBES; ++k) user_probe_push(d, scene.eval(user_shader_probe<false>(k, si, theta)));
+}
+#endif
+
 // One pixel of Shader.forward (shader.py:190-263).  Modes 1, 2, 5 return the
 // un-normalised value; rm_shade_finish applies the global min/max.
 // `theta` (RM_MODE_USER only): the user shader's parameter floats, copied out of the staged block by the caller.
+// `d` (RM_MODE_USER of a shader with probes only): the scene's values at its probe points.
+#ifdef RM_USER_SHADER_PROBES
+RM_DEV Shaded shade_pixel(int mode, const ShadeIn& s, int cmap_size, int degree, const float* theta = nullptr, const float* d = nullptr) {
+#else
 RM_DEV Shaded shade_pixel(int mode, const ShadeIn& s, int cmap_size, int degree, [[maybe_unused]] const float* theta = nullptr) {
+#endif
   switch (mode) {
-#ifdef RM_USER_SHADER
+#ifdef RM_USER_SHADER_PROBES
+    case RM_MODE_USER:
+      return plain(user_shader_fwd<false>(s, theta, d));
+#elif defined(RM_USER_SHADER)
     case RM_MODE_USER:          // (theta: the caller's local array, filled with constant indices, so it dissolves into registers)
       return plain(user_shader_fwd<false>(s, theta));
 #endif
@@ -1162,7 +1208,13 @@ RM_DEV void finish_tile(const RenderArgs& a, const SceneT& scene, const Tetra& T
   float theta[RM_USER_SHADER_PARAMS > 0 ? RM_USER_SHADER_PARAMS : 1] = {};
 #pragma unroll
   for (int i = 0; i < RM_USER_SHADER_PARAMS; ++i) theta[i] = scene.P[RM_USER_SHADER_THETA + i];
+#ifdef RM_USER_SHADER_PROBES
+  float d[RM_USER_SHADER_PROBES] = {};
+  if (mode == RM_MODE_USER) user_probe_values(scene, si, theta, d);      // (mode is uniform: every lane of the wave evaluates)
+  const Shaded sh = shade_pixel(mode, si, a.cmap_size, a.degree, theta, d);
+#else
   const Shaded sh = shade_pixel(mode, si, a.cmap_size, a.degree, theta);
+#endif
 #else
   const Shaded sh = shade_pixel(mode, si, a.cmap_size, a.degree);
 #endif
@@ -2028,7 +2080,23 @@ __global__ void __launch_bounds__(256) RM_BWD_OCC k_render_bwd(RenderArgs a) {
       for (int i = 0; i < RM_USER_SHADER_PARAMS; ++i) theta[i] = scene.P[RM_USER_SHADER_THETA + i];
       const V3 z3 = mk3(0.0f, 0.0f, 0.0f);
       ShadeGrad gs{z3, z3, z3, z3, z3, 0.0f, z3};
+#ifdef RM_USER_SHADER_PROBES
+      // the probe values again (K evaluations: the recording forward writes no buffer for them), the shader's VJP, which also
+      // hands back dL/dd[k], then per probe the scene's VJP at the probe point -- its parameter gradients go where the taps' go,
+      // complete before the reverse march starts -- and the probe's own VJP, which adds to gs and gtheta.  Every lane reaches every
+      // scene.vjp, a lane without a ray with a zero upstream.  Both loops rolled; d / gd indexed by constants only.
+      float d[RM_USER_SHADER_PROBES] = {}, gd[RM_USER_SHADER_PROBES] = {};
+      user_probe_values(scene, si, theta, d);
+      user_shader_vjp<(RM_FAST_VJP != 0)>(si, theta, d, gi3, gs, gtheta, gd);
+#pragma unroll RM_USER_PROBE_UNROLL
+      for (int k = 0; k < RM_USER_SHADER_PROBES; ++k) {
+        const float gk = user_probe_pop(gd);
+        const V3 gq = scene.vjp(user_shader_probe<false>(k, si, theta), live ? gk : 0.0f);
+        user_shader_probe_vjp<(RM_FAST_VJP != 0)>(k, si, theta, gq, gs, gtheta);
+      }
+#else
       user_shader_vjp<(RM_FAST_VJP != 0)>(si, theta, gi3, gs, gtheta);
+#endif
 #pragma unroll
       for (int i = 0; i < RM_USER_SHADER_PARAMS; ++i) scene.st->add(scene.acc0 + RM_USER_SHADER_THETA + i, live ? gtheta[i] : 0.0f);
       gn = gs.n; gv = gs.v; gp_direct = gs.o; gp_surface = gs.p;

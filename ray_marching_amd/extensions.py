@@ -82,6 +82,27 @@ surface_normals) -> [..., 3]`` untouched: called directly, a shader is the user'
 are on.  A (scene, shader) pair is compiled into one library (compiler.compiled_with_shader); the shader's parameters follow the
 scene's in the parameter block and receive their gradients through the same accumulators.
 
+*Scene probes* let a shader ask the SDF questions (ambient occlusion, fixed-step soft shadows, thickness, edge cues, glow):
+``register_shader(..., probes=K)`` with ``1 <= K <= RM_USER_SHADER_MAX_PROBES`` (8).  The source then brings two more functions
+and its own pair takes the probe values,
+
+    template <bool Fast> RM_DEV rm::V3 NAME_probe    (int k, const rm::ShadeIn& s, const float* theta);
+    template <bool Fast> RM_DEV void   NAME_probe_vjp(int k, const rm::ShadeIn& s, const float* theta, rm::V3 gq,
+                                                      rm::ShadeGrad& gs, float* gtheta);
+    template <bool Fast> RM_DEV rm::V3 NAME_fwd(const rm::ShadeIn& s, const float* theta, const float* d);
+    template <bool Fast> RM_DEV void   NAME_vjp(const rm::ShadeIn& s, const float* theta, const float* d, rm::V3 g,
+                                                rm::ShadeGrad& gs, float* gtheta, float* gd);
+
+``NAME_probe`` returns probe ``k``, a point in world space that is a function of the pixel's ``ShadeIn`` and of ``theta`` ONLY: probes
+are independent, none may depend on the value of another (a marched shadow ray, whose next point depends on the last distance,
+is out of scope; fixed-step shadows and fixed-height occlusion are not).  The kernels evaluate ``d[k] = scene(NAME_probe(k, ..))``
+with the full evaluator the normal's taps use and hand ``d`` to ``NAME_fwd``; ``NAME_vjp`` writes ``gtheta[i]`` and ``gd[k] = dL/dd[k]``,
+the kernels turn each ``gd[k]`` into the scene-parameter gradients and ``gq = dL/d(probe k)``, and ``NAME_probe_vjp`` ADDS ``J^T gq``
+into ``gs`` and ``gtheta``.  ``k`` is a run-time value in both (the probe loop stays rolled: one inlined copy of the scene): compute
+with it or select on it, never index an array with it, and index ``d`` / ``gd`` / ``theta`` / ``gtheta`` with constants only (an array
+indexed at run time goes to scratch memory).  The class's PyTorch ``forward`` takes one more trailing argument, ``scene``, a
+callable ``points[..., 3] -> [..., 1]``; with ``probes=0`` (the default) everything is as described above.
+
 Scenes that contain such a leaf, combinator or warp, and frames shaded by such a shader, run only through their per-scene specialised library (specialize.py), into which
 the source is compiled; the LDS interpreter has no handler for them and ``CompiledScene.lib()`` says so instead of
 rendering a wrong picture.
@@ -139,6 +160,7 @@ class UserWarp(_UserSpec):
 class UserShader(_UserSpec):
     kind = "shader"
     sha1: str
+    probes: int = 0     # K: the scene evaluations the shader asks for per pixel (NAME_probe / NAME_probe_vjp); 0: none
 
 
 @dataclass(frozen=True)
@@ -155,6 +177,7 @@ class _Kind:
     device_forward: bool = True     # forward() is replaced by _device_forward (a shader keeps its own)
     out_pair: bool = False          # the source may bring NAME_out_fwd / NAME_out_vjp
     bound: str = ""                 # the noun under which NAME_bound is looked for ("": the kind signs no bound)
+    probe_pair: bool = False        # the source may bring NAME_probe / NAME_probe_vjp (a shader's scene probes)
 
 
 _KINDS = {
@@ -183,8 +206,10 @@ _KINDS = {
         "`template <bool Fast> RM_DEV void NAME_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 g, rm::ShadeGrad& gs, float* "
         "gtheta)`",
         methods=(("forward", "forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals)"),),
-        device_forward=False),
+        same=("sha1", "params", "probes"), device_forward=False, probe_pair=True),
 }
+
+RM_USER_SHADER_MAX_PROBES = 8       # the most scene probes a shader may ask for (d[] / gd[] live in registers: INTEGRATION.md)
 
 _registry: dict[type, _UserSpec] = {}       # registered class -> its registration, of whichever kind
 
@@ -192,9 +217,10 @@ _DEF = r"\b([A-Za-z_]\w*)_%s\s*\("
 
 
 def _parse(kind: str, hip: str):
-    """(NAME, has_out, bounded) of the source of a ``kind``.  NAME is that of the one ``NAME_fwd`` with the kind's return type and
-    must be that of the ``NAME_vjp`` too (of one of them where the kind may bring ``NAME_out_fwd`` / ``NAME_out_vjp``, which come
-    as a pair or not at all and are looked up by their full names, like NAME_bound)."""
+    """(NAME, has_out, bounded, has_probe) of the source of a ``kind``.  NAME is that of the one ``NAME_fwd`` with the kind's return
+    type and must be that of the ``NAME_vjp`` too (of one of them where the kind may bring ``NAME_out_fwd`` / ``NAME_out_vjp``, which
+    come as a pair or not at all and are looked up by their full names, like NAME_bound).  A shader's ``NAME_probe`` /
+    ``NAME_probe_vjp`` are such a pair too: ``NAME_probe_vjp`` is no second shader."""
     row = _KINDS[kind]
     text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
 
@@ -203,6 +229,10 @@ def _parse(kind: str, hip: str):
 
     fwd, vjp = names(row.ret, "fwd"), names("void", "vjp")
     name = next(iter(fwd)) if len(fwd) == 1 else None
+    probe_fwd = probe_vjp = False
+    if row.probe_pair and name is not None:
+        probe_fwd, probe_vjp = name in names(row.ret, "probe"), f"{name}_probe" in vjp
+        vjp = vjp - {f"{name}_probe"}
     if name is None or (name not in vjp if row.out_pair else vjp != fwd):
         raise ValueError(f"hip must define {row.signature}, with one NAME (found fwd: {sorted(fwd)}"
                          + ("" if row.out_pair else f", vjp: {sorted(vjp)}") + ")")
@@ -213,7 +243,11 @@ def _parse(kind: str, hip: str):
                          f"rm::V3& gp, float* gtheta)`: both or neither (found {name}_out_fwd: {out_fwd}, {name}_out_vjp: {out_vjp})")
     if re.search(r"\basm\b|__asm", text):
         raise ValueError(f"a user {kind} must not contain inline assembly (INTEGRATION.md: {kind} contract)")
-    return name, out_fwd, bool(row.bound) and _has_bound(text, name, row.bound)
+    if probe_fwd != probe_vjp:
+        raise ValueError(f"hip may define `template <bool Fast> RM_DEV rm::V3 {name}_probe(int k, const rm::ShadeIn& s, const float* theta)` "
+                         f"and `template <bool Fast> RM_DEV void {name}_probe_vjp(int k, const rm::ShadeIn& s, const float* theta, rm::V3 gq, "
+                         f"rm::ShadeGrad& gs, float* gtheta)`: both or neither (found {name}_probe: {probe_fwd}, {name}_probe_vjp: {probe_vjp})")
+    return name, out_fwd, bool(row.bound) and _has_bound(text, name, row.bound), probe_fwd
 
 
 def _has_bound(text: str, name: str, what: str) -> bool:
@@ -288,7 +322,15 @@ def _register(kind: str, cls, *, params, hip: str, **own):
     params = tuple(params)
     if not all(isinstance(p, str) for p in params) or len(set(params)) != len(params):
         raise ValueError(f"{fn}: params must be distinct attribute names")
-    name, has_out, bounded = _parse(kind, hip)
+    name, has_out, bounded, has_probe = _parse(kind, hip)
+    if row.probe_pair:
+        probes = own["probes"]
+        if isinstance(probes, bool) or not isinstance(probes, int) or not 0 <= probes <= RM_USER_SHADER_MAX_PROBES:
+            raise ValueError(f"{fn}: probes must be an int from 0 to RM_USER_SHADER_MAX_PROBES = {RM_USER_SHADER_MAX_PROBES}, not {probes!r}")
+        if has_probe and probes == 0:
+            raise ValueError(f"{fn}: the source of {cls.__name__} defines {name}_probe / {name}_probe_vjp, but probes=0")
+        if probes > 0 and not has_probe:
+            raise ValueError(f"{fn}: probes={probes}, but the source of {cls.__name__} defines no {name}_probe / {name}_probe_vjp")
     if row.out_pair and has_out != callable(getattr(cls, "out", None)):
         raise TypeError(f"{fn}: {cls.__name__} " + (
             f"has no out(values, points) method, but its source defines {name}_out_fwd / {name}_out_vjp" if has_out else
@@ -305,7 +347,8 @@ def _register(kind: str, cls, *, params, hip: str, **own):
     old = _registry.get(cls)
     if old is not None:
         if any(getattr(old, f) != getattr(spec, f) for f in row.same):
-            raise ValueError(f"{fn}: {cls.__name__} is already registered with different {row.different}")
+            raise ValueError(f"{fn}: {cls.__name__} is already registered with different {row.different}"
+                             + (" (or another number of probes)" if row.probe_pair and old.probes != spec.probes else ""))
         return cls
     for other in _registry.values():
         if other.name == spec.name:          # (a scene's user types and the shader are compiled into one translation unit)
@@ -401,18 +444,22 @@ def warp_child(node, spec: UserWarp):
     return kid
 
 
-def register_shader(cls, *, params=(), hip: str):
+def register_shader(cls, *, params=(), hip: str, probes: int = 0):
     """Make instances of ``cls`` (an ``nn.Module`` subclass) usable as the ``mode`` of ``RenderLoop.forward``: a per-pixel shader
     that runs fused at the end of the frame kernels and in the fused backward.
 
     params: names of ALL its ``nn.Parameter`` attributes in ``named_parameters()`` order (may be empty): ``theta``.
-    hip:    source of NAME_fwd / NAME_vjp (module docstring).
+    hip:    source of NAME_fwd / NAME_vjp (module docstring) and, with ``probes``, of NAME_probe / NAME_probe_vjp.
+    probes: K, the number of scene evaluations the shader asks for per pixel, 0 (none: the default) to
+            RM_USER_SHADER_MAX_PROBES = 8.  With K > 0 the source brings NAME_probe / NAME_probe_vjp, NAME_fwd / NAME_vjp take the
+            probe values ``d`` (and ``gd``), and ``forward`` takes a trailing ``scene`` argument, a callable ``points[..., 3] ->
+            [..., 1]`` (module docstring: "scene probes").
 
     ``cls`` has ``forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals) -> [..., 3]``,
     the first six arguments of the reference's ``Shader.forward`` (``camera_orientation`` [N,4], ``pixel_frames`` [N,3,3]); it is
     the CPU statement of the shader and is NOT replaced.  Registering a class again with the same source is a no-op; with other
-    source or parameters it is an error.  Identifiers are unique across all four kinds (leaves, combinators, warps and shaders)."""
-    return _register("shader", cls, params=params, hip=hip)
+    source, parameters or number of probes it is an error.  Identifiers are unique across all four kinds (leaves, combinators, warps and shaders)."""
+    return _register("shader", cls, params=params, hip=hip, probes=probes)
 
 
 def shader_spec(node):

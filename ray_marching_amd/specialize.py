@@ -171,18 +171,35 @@ def _warp_section(cs: CompiledScene) -> str:
 
 
 def _shader_section(cs: CompiledScene) -> str:
-    """The user shader's source and the two functions the frame kernels call, for the header's inclusion from csrc/rm_kernels.h
-    (behind rm::ShadeIn / rm::ShadeGrad, inside namespace rm)."""
+    """The user shader's source and the functions the frame kernels call, for the header's inclusion from csrc/rm_kernels.h
+    (behind rm::ShadeIn / rm::ShadeGrad, inside namespace rm): two, or -- a shader with scene probes, RM_USER_SHADER_PROBES --
+    four, of which user_shader_fwd / user_shader_vjp then carry the probe values."""
     name, floats, sha = cs.user_shader
+    k = cs.user_shader_probes
+    head = ("#define RM_USER_SHADER 1\n"
+            f"#define RM_USER_SHADER_THETA {cs.shader_offset}\n"
+            f"#define RM_USER_SHADER_PARAMS {floats}\n")
+    if not k:
+        return (
+            head
+            + f"// user shader: {name}, {floats} parameter floats, sha1 {sha}\n{cs.user_shader_source.strip()}\n"
+            "template <bool Fast> RM_DEV V3 user_shader_fwd(const ShadeIn& s, const float* theta) {\n"
+            f"  return {name}_fwd<Fast>(s, theta);\n}}\n"
+            "template <bool Fast> RM_DEV void user_shader_vjp(const ShadeIn& s, const float* theta, V3 g, ShadeGrad& gs, float* gtheta) {\n"
+            f"  {name}_vjp<Fast>(s, theta, g, gs, gtheta);\n}}\n")
     return (
-        "#define RM_USER_SHADER 1\n"
-        f"#define RM_USER_SHADER_THETA {cs.shader_offset}\n"
-        f"#define RM_USER_SHADER_PARAMS {floats}\n"
-        f"// user shader: {name}, {floats} parameter floats, sha1 {sha}\n{cs.user_shader_source.strip()}\n"
-        "template <bool Fast> RM_DEV V3 user_shader_fwd(const ShadeIn& s, const float* theta) {\n"
-        f"  return {name}_fwd<Fast>(s, theta);\n}}\n"
-        "template <bool Fast> RM_DEV void user_shader_vjp(const ShadeIn& s, const float* theta, V3 g, ShadeGrad& gs, float* gtheta) {\n"
-        f"  {name}_vjp<Fast>(s, theta, g, gs, gtheta);\n}}\n")
+        head + f"#define RM_USER_SHADER_PROBES {k}\n"
+        + f"// user shader: {name}, {floats} parameter floats, {k} scene probes, sha1 {sha}\n{cs.user_shader_source.strip()}\n"
+        "template <bool Fast> RM_DEV V3 user_shader_probe(int k, const ShadeIn& s, const float* theta) {\n"
+        f"  return {name}_probe<Fast>(k, s, theta);\n}}\n"
+        "template <bool Fast> RM_DEV void user_shader_probe_vjp(int k, const ShadeIn& s, const float* theta, V3 gq, ShadeGrad& gs, "
+        "float* gtheta) {\n"
+        f"  {name}_probe_vjp<Fast>(k, s, theta, gq, gs, gtheta);\n}}\n"
+        "template <bool Fast> RM_DEV V3 user_shader_fwd(const ShadeIn& s, const float* theta, const float* d) {\n"
+        f"  return {name}_fwd<Fast>(s, theta, d);\n}}\n"
+        "template <bool Fast> RM_DEV void user_shader_vjp(const ShadeIn& s, const float* theta, const float* d, V3 g, ShadeGrad& gs, "
+        "float* gtheta, float* gd) {\n"
+        f"  {name}_vjp<Fast>(s, theta, d, g, gs, gtheta, gd);\n}}\n")
 
 
 def user_names(cs: CompiledScene):
