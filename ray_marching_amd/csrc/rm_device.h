@@ -1191,8 +1191,10 @@ struct Scene {
 RM_DEV float ld_t(const void* base, int64_t i, int dt);
 // Bounding sphere (centre, radius) of the surface of the subtree encoded by instructions [begin, end),
 // in the frame in which that subtree is evaluated: subtree(p) >= |p - c| - R for every p.  R = +inf
-// when no finite bound is known (plane, strongly non-unit affine quaternion, non-positive blend_k, odd
-// parameters).  Runs once per block on one thread, from the parameters already staged in LDS.
+// when no finite bound is known (plane, strongly non-unit affine quaternion, non-positive or infinite blend_k, odd
+// parameters).  A NaN in any parameter the subtree reads, and a capsule of length zero, give R = Ru = +inf: the node is NaN
+// where a bound would promise a number (restated in float64 in oracle/bound_ref.py, pinned by tests/test_scene_bounds.py).
+// Runs once per block on one thread, from the parameters already staged in LDS.
 struct BoundFrame {
   float cx, cy, cz, R;   // union frames: enclosing sphere of the children folded so far
   float slope;           // union frames: smallest slope among them
@@ -1248,7 +1250,10 @@ RM_DEV void subtree_bound(GetIns ins, const float* P, int begin, int end, float*
         cx = 0.5f * (a[0] + a[3]); cy = 0.5f * (a[1] + a[4]); cz = 0.5f * (a[2] + a[5]);
         float hx = 0.5f * (a[3] - a[0]), hy = 0.5f * (a[4] - a[1]), hz = 0.5f * (a[5] - a[2]);
         slope = uslope = 1.0f;
-        R = Ru = (a[6] >= 0.0f) ? sqrtf(hx * hx + hy * hy + hz * hz) * 1.00001f + a[6] : inf;
+        // start == end: AB / |AB|^2 is 0 / 0 and the value NaN at every point (len2 as derive_line_constants forms it)
+        float abx = a[3] - a[0], aby = a[4] - a[1], abz = a[5] - a[2];
+        float len2 = (abx * abx + aby * aby) + abz * abz;
+        R = Ru = (a[6] >= 0.0f && len2 > 0.0f) ? sqrtf(hx * hx + hy * hy + hz * hz) * 1.00001f + a[6] : inf;
       } break;
       case RM_OP_DISK: cx = cy = cz = 0.0f; slope = uslope = 1.0f; R = Ru = (P[off] >= 0.0f) ? P[off] : inf; break;
       case RM_OP_TORUS:
@@ -1258,10 +1263,12 @@ RM_DEV void subtree_bound(GetIns ins, const float* P, int begin, int end, float*
       case RM_OP_ROUND:                                                         // d - r <= ub + max(-r, 0)
         Ru += fmaxf(-P[off], 0.0f);
         R += fmaxf(P[off], 0.0f);                                               // d - r >= d - max(r, 0)
+        if (P[off] != P[off]) R = Ru = inf;                                     // (fmaxf drops a NaN r; the value is NaN everywhere)
         break;
       case RM_OP_ONION:                                                         // |d| <= uslope |p - c| + max(Ru, R)  (d >= -R)
         Ru = fmaxf(Ru, R) + fmaxf(-P[off], 0.0f);
         R += fmaxf(P[off], 0.0f);                                               // |d| - r >= d - max(r, 0)
+        if (P[off] != P[off]) R = Ru = inf;                                     // (as for ROUND)
         break;
       case RM_OP_AFFINE_PUSH:
         if (sp >= kDepth) { overflow = true; break; }
@@ -1317,11 +1324,11 @@ RM_DEV void subtree_bound(GetIns ins, const float* P, int begin, int end, float*
         --sp; cx = st[sp].cx; cy = st[sp].cy; cz = st[sp].cz; R = st[sp].R; slope = st[sp].slope;
         Ru = inf; uslope = 1.0f;
         break;
-      case RM_OP_SMOOTH_END: {   // -lse(-k d)/k >= min d - log(n)/k  for k > 0
+      case RM_OP_SMOOTH_END: {   // -lse(-k d)/k >= min d - log(n)/k  for 0 < k < inf
         --sp; cx = st[sp].cx; cy = st[sp].cy; cz = st[sp].cz; R = st[sp].R; slope = st[sp].slope;
         Ru = inf; uslope = 1.0f;
         float k = P[off];
-        R = (k > 0.0f) ? R + logf((float)st[sp].n) / k : inf;
+        R = (k > 0.0f && k < inf) ? R + logf((float)st[sp].n) / k : inf;      // (k = +inf: -lse(-k d) / k is NaN everywhere)
       } break;
 #ifdef RM_USER_COMBINATORS
       // a user combinator signs no bound (yet): nothing is known about its value, whatever its children's spheres were.

@@ -51,7 +51,21 @@ def scene_cache(cs: CompiledScene, dev, stream):
         buf = torch.full((cs.n_params + cs.n_derived,), -1, dtype=torch.int32, device=dev).view(torch.float32)
         caches[key] = buf
     return buf
-bwd_clear_flags = _abi.FLAG_DYNAMIC_TILES if os.environ.get("RM_BWD_STATIC_TILES", "0") == "1" else 0      # A/B knob
+
+
+def staged_block(cs: CompiledScene, device=None):
+    """A copy of the scene block (the parameters, then the derived constants: capsule constants, cull bounds, bound tables)
+    that the last inference frame on the current stream left in its scene cache, or None when there is none: what the
+    frame kernels staged, for looking at (tests/test_scene_bounds.py)."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    index = torch.cuda.current_device() if dev.index is None else dev.index
+    with torch.cuda.device(index):
+        stream = _abi.current_stream(dev)
+    buf = cs.__dict__.get("_block_caches", {}).get((index, int(getattr(stream, "value", stream) or 0)))
+    return None if buf is None else buf.clone()
+
+
+bwd_clear_flags =_abi.FLAG_DYNAMIC_TILES if os.environ.get("RM_BWD_STATIC_TILES", "0") == "1" else 0      # A/B knob
 use_forward_block = os.environ.get("RM_FORWARD_BLOCK", "1") != "0"      # A/B knob: backward kernels take the forward's scene block
 
 

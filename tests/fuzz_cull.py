@@ -5,7 +5,8 @@ compiled with a cull test in front of EVERY boundable union child (RM_CULL_MIN_C
 over the points, reduced per block: the longer program changes the interpreter's LDS footprint and with it the
 block size rm_abi.hip picks, so their partial sums may be grouped differently -- they are compared to 1e-3 of
 the largest component plus 2e-6 of the scene's largest gradient instead (found by this fuzz: 11 of 134 trees, values and point gradients identical).
-    python tests/fuzz_cull.py [n_seeds]        (a script, not collected by pytest: ~1 s per tree)"""
+    python tests/fuzz_cull.py [n_seeds]        (a script, not collected by pytest: ~1 s per tree)
+FUZZ_WIDEN=1 draws the trees through helpers.widen_spec as well (negative rounding / onion, |q|^2 in 0.77 .. 1.9)."""
 import os, sys
 root = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
@@ -25,6 +26,8 @@ seeds = [int(x) for x in os.environ['FUZZ_SEEDS'].split(',')] if os.environ.get(
 for seed in seeds:
     gen = torch.Generator().manual_seed(900000 + seed)
     spec = O.map_spec(H.random_spec(gen), lambda x: x.clone().float())
+    if os.environ.get("FUZZ_WIDEN"):        # negative rounding / onion, |q|^2 in 0.77 .. 1.9 (helpers.widen_spec; its own stream)
+        spec = H.widen_spec(spec, torch.Generator().manual_seed(1900000 + seed))
     scale = float(torch.rand(1, generator=gen) * 3 + 0.2)
     pts = torch.cat([(torch.rand(8192, 3, generator=gen) * 2 - 1) * 6 * scale, (torch.rand(8192, 3, generator=gen) * 2 - 1) * scale]).to(dev)
     wts = torch.randn(pts.shape[0], 1, generator=gen).to(dev)

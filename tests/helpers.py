@@ -144,6 +144,34 @@ def random_spec(gen, depth=0, max_depth=4):
     return ("onion", {"radius": u(0.02, 0.2).clone()}, random_spec(gen, depth + 1, max_depth))
 
 
+def widen_spec(spec, gen):
+    """A tree of random_spec pushed into the parameter ranges that function never draws: every `rounding` / `onion` parameter
+    is negated with probability 0.4, every affine quaternion rescaled with probability 0.5 to the norm 0.88 + 0.5 u, i.e.
+    |q|^2 in 0.77 .. 1.9 (the slopes min(1, 2 s - 1) and max(1, 2 s - 1) of the bound walk both leave 1).  Every |q|^2 stays
+    0.01 away from 0.75 and 4, where the walk gives up, so that fp32 and fp64 decide finite versus inf alike.  Draws from
+    `gen` only; returns a new spec."""
+    def u():
+        return float(torch.rand(1, generator=gen))
+
+    kind, prm = spec[0], dict(spec[1])
+    if kind in ("rounding", "onion"):
+        name = "rounding" if kind == "rounding" else "radius"
+        if u() < 0.4:
+            prm[name] = -prm[name]
+    if kind == "affine":
+        q = prm["orientation"]
+        if u() < 0.5:
+            q = torch.nn.functional.normalize(q, dim=0) * (0.88 + 0.5 * u())
+        s2 = float(q.double().pow(2).sum())
+        assert abs(s2 - 0.75) >= 0.01 and abs(s2 - 4.0) >= 0.01, s2
+        prm["orientation"] = q
+    if kind in ("affine", "rounding", "onion"):
+        return (kind, prm, widen_spec(spec[2], gen))
+    if kind in ("smooth_union", "union"):
+        return (kind, prm, [widen_spec(c, gen) for c in spec[2]])
+    return (kind, prm)
+
+
 def spec_has(spec, kind):
     if spec[0] == kind:
         return True
