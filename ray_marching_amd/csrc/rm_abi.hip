@@ -356,6 +356,10 @@ int64_t rm_wave_tiles(int32_t num_cameras, int32_t rows, int32_t width, int32_t 
   return wave_tile_count(num_cameras, rows, width, flags);
 }
 
+// A frame kernel: the instantiation is chosen once per call; pick_launch, the occupancy query and the launch take it from there
+using RenderKernel = void (*)(rm::RenderArgs);
+constexpr int kMaxMode = rm::UserShader::kEnabled ? RM_MODE_USER : 7;   // RM_MODE_USER only where a user shader was compiled in
+
 int rm_render_forward(const RmScene* scene, const RmCamera* cam, const RmTetra* tetra, const void* orientation,
                       const void* translation, void* image, int32_t image_dtype, float* first_pass, float* p_final,
                       float* traj, int32_t* nexec, float* normal_u, uint32_t* minmax, const void* cmap, int32_t cmap_size,
@@ -364,11 +368,7 @@ int rm_render_forward(const RmScene* scene, const RmCamera* cam, const RmTetra* 
                       float* park_ws, int64_t park_capacity, void* stream) {
   if (int e = check_render(scene, cam, tetra, orientation, translation, steps, row_begin, row_end)) return e;
   if (!image) return fail(RM_E_BADARG, "rm_render_forward: null image");
-#ifdef RM_USER_SHADER
-  if (mode < 0 || mode > RM_MODE_USER) return fail(RM_E_BADARG, "rm_render_forward: mode %d not in 0..8", mode);
-#else
-  if (mode < 0 || mode > 7) return fail(RM_E_BADARG, "rm_render_forward: mode %d not in 0..7", mode);
-#endif
+  if (mode < 0 || mode > kMaxMode) return fail(RM_E_BADARG, "rm_render_forward: mode %d not in 0..%d", mode, kMaxMode);
   const bool global = (mode == RM_MODE_DISTANCE || mode == RM_MODE_PROXIMITY || mode == RM_MODE_LAPLACIAN);
   const bool mapped = (mode == RM_MODE_TANGENT || mode == RM_MODE_SPIN);
   if (global && (!minmax || !first_pass))
@@ -434,9 +434,9 @@ int rm_render_forward(const RmScene* scene, const RmCamera* cam, const RmTetra* 
   }
   // two instantiations: the plain inference frame, and the one that also records (trajectory / p_final / nexec / normal_u)
   const bool rec = traj || p_final || nexec || normal_u;
+  const RenderKernel kernel = rec ? rm::k_render_fwd<GF, true> : rm::k_render_fwd<GF, false>;
   Launch L;
-  if (int e = rec ? pick_launch(rm::k_render_fwd<GF, true>, *scene, false, tune_block(), &L)
-                  : pick_launch(rm::k_render_fwd<GF, false>, *scene, false, tune_block(), &L)) return e;
+  if (int e = pick_launch(kernel, *scene, false, tune_block(), &L)) return e;
   int64_t tiles = (wave_tiles + (L.block >> 6) - 1) / (L.block >> 6);
   int grid = tune_max_blocks() > 0 ? grid_for(tiles, tune_max_blocks()) : (int)tiles;
   if (tune_max_blocks() > 0 && (flags & RM_FLAG_DYNAMIC_TILES) && minmax && !env_set("RM_MAX_BLOCKS")) {
@@ -446,17 +446,14 @@ int rm_render_forward(const RmScene* scene, const RmCamera* cam, const RmTetra* 
     // band); (2) at least ~2 tiles per wave, or the dynamic queues have nothing to balance with (512^2 frame,
     // closed scene 1: 1280 -> 512 blocks, 228 -> 177 us).
     int per_cu = 0;
-    const hipError_t oe = rec ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rm::k_render_fwd<GF, true>, L.block, L.lds)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rm::k_render_fwd<GF, false>, L.block, L.lds);
-    if (oe == hipSuccess && per_cu > 0) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, L.block, L.lds) == hipSuccess && per_cu > 0) {
       const int resident = per_cu * cu_count();
       if (grid > resident) grid = resident;
     }
     const int64_t two_per_wave = (wave_tiles / 2 + (L.block >> 6) - 1) / (L.block >> 6);
     if (grid > two_per_wave) grid = (int)(two_per_wave < 1 ? 1 : two_per_wave);
   }
-  if (rec) rm::k_render_fwd<GF, true><<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
-  else rm::k_render_fwd<GF, false><<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
+  kernel<<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
   if (int e = launched("k_render_fwd")) return e;
   if (park) {
     Launch LP;
@@ -590,6 +587,21 @@ int rm_camera_backward(const RmCamera* cam, const float* orientation, const floa
   return launched("k_camera_bwd_finish");
 }
 
+#ifndef RM_NO_BACKWARD
+// k_render_bwd for a shader mode: one instantiation per kind (rm_kernels.h)
+static RenderKernel render_bwd_kernel(int mode) {
+  switch (mode) {
+    case RM_MODE_LAPLACIAN: return rm::k_render_bwd<GB, 1>;
+    case RM_MODE_PROXIMITY: return rm::k_render_bwd<GB, 2>;
+    case RM_MODE_DISTANCE: return rm::k_render_bwd<GB, 3>;
+#ifdef RM_USER_SHADER
+    case RM_MODE_USER: return rm::k_render_bwd<GB, 4>;
+#endif
+    default: return rm::k_render_bwd<GB, 0>;
+  }
+}
+#endif
+
 int rm_render_backward(const RmScene* scene, const RmCamera* cam, const RmTetra* tetra, const float* orientation,
                        const float* translation, const float* traj, const int32_t* nexec, const float* p_final,
                        const float* normal_u, const float* grad_image, float* grad_params, float* partials, uint32_t* work,
@@ -603,13 +615,7 @@ int rm_render_backward(const RmScene* scene, const RmCamera* cam, const RmTetra*
   if (int e = check_render(scene, cam, tetra, orientation, translation, steps, row_begin, row_end)) return e;
   if (cam->dtype != RM_DTYPE_F32) return fail(RM_E_BADARG, "rm_render_backward: fp32 camera buffers only");
   const bool mapped = (mode == RM_MODE_TANGENT || mode == RM_MODE_SPIN);
-#ifdef RM_USER_SHADER
-  if (mode < 0 || mode > RM_MODE_USER) return fail(RM_E_BADARG, "rm_render_backward: mode %d not in 0..8", mode);
-  const int kind = (mode == RM_MODE_LAPLACIAN) ? 1 : (mode == RM_MODE_PROXIMITY ? 2 : (mode == RM_MODE_DISTANCE ? 3 : (mode == RM_MODE_USER ? 4 : 0)));
-#else
-  if (mode < 0 || mode > 7) return fail(RM_E_BADARG, "rm_render_backward: mode %d not in 0..7", mode);
-  const int kind = (mode == RM_MODE_LAPLACIAN) ? 1 : (mode == RM_MODE_PROXIMITY ? 2 : (mode == RM_MODE_DISTANCE ? 3 : 0));
-#endif
+  if (mode < 0 || mode > kMaxMode) return fail(RM_E_BADARG, "rm_render_backward: mode %d not in 0..%d", mode, kMaxMode);
   if (mapped && (!cmap || cmap_size <= 0 || cmap_dtype < RM_DTYPE_F32 || cmap_dtype > RM_DTYPE_F64))
     return fail(RM_E_BADARG, "rm_render_backward: mode %d needs the colormap of the forward call", mode);
   if (!p_final || !grad_image || !partials || (steps > 0 && !traj)) return fail(RM_E_BADARG, "rm_render_backward: null buffer");
@@ -623,20 +629,10 @@ int rm_render_backward(const RmScene* scene, const RmCamera* cam, const RmTetra*
   a.grad_pos = grad_pos; a.grad_dirs = grad_dirs; a.grad_qdir = grad_qdir; a.tile_cost = tile_cost;
   a.cmap = cmap; a.cmap_size = cmap_size; a.cmap_dtype = cmap_dtype; a.degree = degree;
   a.mode = mode; a.steps = steps; a.row_begin = row_begin; a.row_end = row_end; a.flags = flags & (RM_FLAG_TILE8X8 | RM_FLAG_DYNAMIC_TILES | RM_FLAG_EARLY_OUT);
+  const RenderKernel kernel = render_bwd_kernel(mode);
   Launch L;
-  if (int e = kind == 1 ? pick_launch(rm::k_render_bwd<GB, 1>, *scene, true, 128, &L)
-            : kind == 2 ? pick_launch(rm::k_render_bwd<GB, 2>, *scene, true, 128, &L)
-            : kind == 3 ? pick_launch(rm::k_render_bwd<GB, 3>, *scene, true, 128, &L)
-#ifdef RM_USER_SHADER
-            : kind == 4 ? pick_launch(rm::k_render_bwd<GB, 4>, *scene, true, 128, &L)
-#endif
-                        : pick_launch(rm::k_render_bwd<GB, 0>, *scene, true, 128, &L)) return e;
-  int64_t wave_tiles;
-  {
-    const int W = cam->width, rows = row_end - row_begin;
-    wave_tiles = (flags & RM_FLAG_TILE8X8) ? (int64_t)cam->num_cameras * ((W + 7) >> 3) * ((rows + 7) >> 3)
-                                           : ((int64_t)cam->num_cameras * rows * W + 63) / 64;
-  }
+  if (int e = pick_launch(kernel, *scene, true, 128, &L)) return e;
+  const int64_t wave_tiles = wave_tile_count(cam->num_cameras, row_end - row_begin, cam->width, flags);
   int grid = grid_for((wave_tiles + (L.block >> 6) - 1) / (L.block >> 6), tune_bwd_blocks());
   // Two tiles per wave or fewer (config 4 at 512^2: 4096 tiles, 2048 waves): the tile queues have nothing to balance, and
   // every wave would end on a look at all of them -- static stride instead (same-box: 0.340 -> 0.329 ms per step at 512^2;
@@ -662,13 +658,7 @@ int rm_render_backward(const RmScene* scene, const RmCamera* cam, const RmTetra*
     a.hard_slot = a.hard_ray + c4;
     a.hard_step = a.hard_slot + c4;
   }
-  if (kind == 1) rm::k_render_bwd<GB, 1><<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
-  else if (kind == 2) rm::k_render_bwd<GB, 2><<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
-  else if (kind == 3) rm::k_render_bwd<GB, 3><<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
-#ifdef RM_USER_SHADER
-  else if (kind == 4) rm::k_render_bwd<GB, 4><<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
-#endif
-  else rm::k_render_bwd<GB, 0><<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
+  kernel<<<grid, L.block, L.lds, (hipStream_t)stream>>>(a);
   if (int e = launched("k_render_bwd")) return e;
   int rows = grid;
   if (defer) {

@@ -489,6 +489,42 @@ struct LeafBound {
 #undef RM_STATIC_CODE_LEAVES
 #endif
 
+// The parameter window of a user node: its n (<= N) floats out of the staged block, zero-padded to N, and the zeroed gradient
+// array its VJP fills.  n and off are constants under StaticProgram: v[] / g[] are indexed by constants only and dissolve.
+template <int N>
+struct UserTheta {
+  float v[N > 0 ? N : 1], g[N > 0 ? N : 1];
+  template <class PT> RM_DEV UserTheta(const PT& P, int off, int n) : v{}, g{} {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = (i < n) ? P[off + i] : 0.0f;
+  }
+  template <class S> RM_DEV void flush(S& s, int off, int n) const {   // g[] into the parameters' accumulators
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+      if (i < n) padd(s, s.acc0 + off + i, g[i]);
+  }
+};
+
+// The frame stack of the affine pair and of the user warps: the forward machine saves p, the reverse machine p and gp.
+template <class S> RM_DEV void push_point(S& s) {
+  s.st->st(s.sp, s.p.x); s.st->st(s.sp + 1, s.p.y); s.st->st(s.sp + 2, s.p.z);
+  s.sp += 3;
+}
+template <class S> RM_DEV void pop_point(S& s) {
+  s.sp -= 3;
+  s.p = mk3(s.st->ld(s.sp), s.st->ld(s.sp + 1), s.st->ld(s.sp + 2));
+}
+template <class S> RM_DEV void push_frame(S& s) {
+  s.st->st(s.sp, s.p.x); s.st->st(s.sp + 1, s.p.y); s.st->st(s.sp + 2, s.p.z);
+  s.st->st(s.sp + 3, s.gp.x); s.st->st(s.sp + 4, s.gp.y); s.st->st(s.sp + 5, s.gp.z);
+  s.sp += 6;
+}
+template <class S> RM_DEV void pop_frame(S& s, V3& p, V3& gp) {
+  s.sp -= 6;
+  p = mk3(s.st->ld(s.sp), s.st->ld(s.sp + 1), s.st->ld(s.sp + 2));
+  gp = mk3(s.st->ld(s.sp + 3), s.st->ld(s.sp + 4), s.st->ld(s.sp + 5));
+}
+
 // User-defined combinators (RM_OP_USER_FOLD / RM_OP_USER_END; extensions.register_combinator).  The same first inclusion of
 // the code header brings, independently of the leaves, #define RM_USER_COMBINATORS <types>, RM_USER_COMB_MAX_PARAMS, the
 // combinators' own device functions
@@ -503,23 +539,20 @@ struct LeafBound {
 #ifdef RM_USER_COMBINATORS
 template <int A0, int N, int NP, class S, class PT>
 RM_DEV void user_end_fwd(S& s, const PT& P, int off, int type) {
-  float d[N], theta[NP > 0 ? NP : 1] = {};
+  float d[N];
+  const UserTheta<NP> theta(P, off, NP);
 #pragma unroll
   for (int i = 0; i < N; ++i) d[i] = s.st->ld(s.tape0 + A0 + i);
-#pragma unroll
-  for (int i = 0; i < NP; ++i) theta[i] = P[off + i];
-  s.d = user_comb_fwd<S::kFast, N>(type, d, theta);
+  s.d = user_comb_fwd<S::kFast, N>(type, d, theta.v);
 }
 template <int A0, int N, int NP, class S, class PT>
 RM_DEV void user_end_bwd(S& s, const PT& P, int off, int type) {
-  float d[N], gd[N], theta[NP > 0 ? NP : 1] = {}, gtheta[NP > 0 ? NP : 1] = {};
+  float d[N], gd[N];
+  UserTheta<NP> theta(P, off, NP);
 #pragma unroll
   for (int i = 0; i < N; ++i) { d[i] = s.st->ld(s.tape0 + A0 + i); gd[i] = 0.0f; }
-#pragma unroll
-  for (int i = 0; i < NP; ++i) theta[i] = P[off + i];
-  user_comb_vjp<S::kFast, N>(type, d, theta, s.g, gd, gtheta);
-#pragma unroll
-  for (int i = 0; i < NP; ++i) padd(s, s.acc0 + off + i, gtheta[i]);
+  user_comb_vjp<S::kFast, N>(type, d, theta.v, s.g, gd, theta.g);
+  theta.flush(s, off, NP);
 #pragma unroll
   for (int i = 0; i < N; ++i) s.st->st(s.tape0 + A0 + N + i, gd[i]);
 }
@@ -562,10 +595,8 @@ RM_DEV void fwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
       break;
 #ifdef RM_USER_LEAVES
     case RM_OP_USER: {  // a0 = leaf type, a1 = parameter floats: constants under StaticProgram, so theta[] dissolves into P's registers
-      float theta[RM_USER_MAX_PARAMS];
-#pragma unroll
-      for (int i = 0; i < RM_USER_MAX_PARAMS; ++i) theta[i] = (i < a1) ? P[off + i] : 0.0f;
-      s.d = user_leaf_fwd<S::kFast>(a0, s.p, theta);
+      const UserTheta<RM_USER_MAX_PARAMS> theta(P, off, a1);
+      s.d = user_leaf_fwd<S::kFast>(a0, s.p, theta.v);
     } break;
 #endif
     case RM_OP_LINE: {  // capsule; derived block holds AB and AB/|AB|^2
@@ -584,14 +615,12 @@ RM_DEV void fwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
       s.d = norm2_t<S::kFast>(ring, s.p.y) - P[off + 1];
     } break;
     case RM_OP_AFFINE_PUSH: {  // child(rot(p - t, conj(q)))
-      s.st->st(s.sp, s.p.x); s.st->st(s.sp + 1, s.p.y); s.st->st(s.sp + 2, s.p.z);
-      s.sp += 3;
+      push_point(s);
       V3 t = P.v3(off);
       s.p = qrot(s.p - t, P[off + 3], neg(P.v3(off + 4)));
     } break;
     case RM_OP_AFFINE_POP:
-      s.sp -= 3;
-      s.p = mk3(s.st->ld(s.sp), s.st->ld(s.sp + 1), s.st->ld(s.sp + 2));
+      pop_point(s);
       break;
     case RM_OP_UNION_BEGIN:
       s.st->st(s.sp, s.acc); s.sp += 1;
@@ -652,22 +681,16 @@ RM_DEV void fwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
 #endif
 #ifdef RM_USER_WARPS
     case RM_OP_USER_PUSH: {  // a0 = warp type, a1 = parameter floats: child(NAME_fwd(p, theta))
-      float theta[RM_USER_WARP_MAX_PARAMS];
-#pragma unroll
-      for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i) theta[i] = (i < a1) ? P[off + i] : 0.0f;
-      s.st->st(s.sp, s.p.x); s.st->st(s.sp + 1, s.p.y); s.st->st(s.sp + 2, s.p.z);
-      s.sp += 3;
-      s.p = user_warp_fwd<S::kFast>(a0, s.p, theta);
+      const UserTheta<RM_USER_WARP_MAX_PARAMS> theta(P, off, a1);
+      push_point(s);
+      s.p = user_warp_fwd<S::kFast>(a0, s.p, theta.v);
     } break;
     case RM_OP_USER_POP:  // a1 = parameter floats << 16 | (value slot + 1, 0: the type has no `out`)
-      s.sp -= 3;
-      s.p = mk3(s.st->ld(s.sp), s.st->ld(s.sp + 1), s.st->ld(s.sp + 2));
+      pop_point(s);
       if ((a1 & 65535) != 0) {
-        float theta[RM_USER_WARP_MAX_PARAMS];
-#pragma unroll
-        for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i) theta[i] = (i < (a1 >> 16)) ? P[off + i] : 0.0f;
+        const UserTheta<RM_USER_WARP_MAX_PARAMS> theta(P, off, a1 >> 16);
         if (s.record) s.st->st(s.tape0 + (a1 & 65535) - 1, s.d);
-        s.d = user_warp_out_fwd<S::kFast>(a0, s.d, s.p, theta);
+        s.d = user_warp_out_fwd<S::kFast>(a0, s.d, s.p, theta.v);
       }
       break;
 #endif
@@ -770,13 +793,9 @@ RM_DEV void bwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
       break;
 #ifdef RM_USER_LEAVES
     case RM_OP_USER: {
-      float theta[RM_USER_MAX_PARAMS], gtheta[RM_USER_MAX_PARAMS];
-#pragma unroll
-      for (int i = 0; i < RM_USER_MAX_PARAMS; ++i) { theta[i] = (i < a1) ? P[off + i] : 0.0f; gtheta[i] = 0.0f; }
-      user_leaf_vjp<S::kFast>(a0, s.p, theta, s.g, s.gp, gtheta);
-#pragma unroll
-      for (int i = 0; i < RM_USER_MAX_PARAMS; ++i)
-        if (i < a1) padd(s, A + off + i, gtheta[i]);
+      UserTheta<RM_USER_MAX_PARAMS> theta(P, off, a1);
+      user_leaf_vjp<S::kFast>(a0, s.p, theta.v, s.g, s.gp, theta.g);
+      theta.flush(s, off, a1);
     } break;
 #endif
     case RM_OP_LINE: {
@@ -820,17 +839,13 @@ RM_DEV void bwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
       padd(s, A + off + 1, -s.g);
     } break;
     case RM_OP_AFFINE_POP: {  // reverse order: enter the child frame
-      s.st->st(s.sp, s.p.x); s.st->st(s.sp + 1, s.p.y); s.st->st(s.sp + 2, s.p.z);
-      s.st->st(s.sp + 3, s.gp.x); s.st->st(s.sp + 4, s.gp.y); s.st->st(s.sp + 5, s.gp.z);
-      s.sp += 6;
+      push_frame(s);
       s.p = qrot(s.p - P.v3(off), P[off + 3], neg(P.v3(off + 4)));
       s.gp = mk3(0.0f, 0.0f, 0.0f);
     } break;
     case RM_OP_AFFINE_PUSH: {  // reverse order: leave the child frame, pull gp back
-      V3 gl = s.gp;
-      s.sp -= 6;
-      V3 po = mk3(s.st->ld(s.sp), s.st->ld(s.sp + 1), s.st->ld(s.sp + 2));
-      V3 gpo = mk3(s.st->ld(s.sp + 3), s.st->ld(s.sp + 4), s.st->ld(s.sp + 5));
+      V3 gl = s.gp, po, gpo;
+      pop_frame(s, po, gpo);
       float w = P[off + 3];
       V3 u = neg(P.v3(off + 4));
       V3 v = po - P.v3(off);
@@ -901,38 +916,23 @@ RM_DEV void bwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
 #endif
 #ifdef RM_USER_WARPS
     case RM_OP_USER_POP: {  // reverse order: the `out` first (s.g becomes the child's upstream), then enter the child frame
-      float theta[RM_USER_WARP_MAX_PARAMS];
-#pragma unroll
-      for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i) theta[i] = (i < (a1 >> 16)) ? P[off + i] : 0.0f;
+      UserTheta<RM_USER_WARP_MAX_PARAMS> theta(P, off, a1 >> 16);
       if ((a1 & 65535) != 0) {
-        float gtheta[RM_USER_WARP_MAX_PARAMS];
-#pragma unroll
-        for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i) gtheta[i] = 0.0f;
         float gd = 0.0f;
-        user_warp_out_vjp<S::kFast>(a0, s.st->ld(s.tape0 + (a1 & 65535) - 1), s.p, theta, s.g, gd, s.gp, gtheta);
+        user_warp_out_vjp<S::kFast>(a0, s.st->ld(s.tape0 + (a1 & 65535) - 1), s.p, theta.v, s.g, gd, s.gp, theta.g);
         s.g = gd;
-#pragma unroll
-        for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i)
-          if (i < (a1 >> 16)) padd(s, A + off + i, gtheta[i]);
+        theta.flush(s, off, a1 >> 16);
       }
-      s.st->st(s.sp, s.p.x); s.st->st(s.sp + 1, s.p.y); s.st->st(s.sp + 2, s.p.z);
-      s.st->st(s.sp + 3, s.gp.x); s.st->st(s.sp + 4, s.gp.y); s.st->st(s.sp + 5, s.gp.z);
-      s.sp += 6;
-      s.p = user_warp_fwd<S::kFast>(a0, s.p, theta);
+      push_frame(s);
+      s.p = user_warp_fwd<S::kFast>(a0, s.p, theta.v);
       s.gp = mk3(0.0f, 0.0f, 0.0f);
     } break;
     case RM_OP_USER_PUSH: {  // reverse order: leave the child frame, pull gp back through the map
-      float theta[RM_USER_WARP_MAX_PARAMS], gtheta[RM_USER_WARP_MAX_PARAMS];
-#pragma unroll
-      for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i) { theta[i] = (i < a1) ? P[off + i] : 0.0f; gtheta[i] = 0.0f; }
+      UserTheta<RM_USER_WARP_MAX_PARAMS> theta(P, off, a1);
       const V3 gl = s.gp;
-      s.sp -= 6;
-      s.p = mk3(s.st->ld(s.sp), s.st->ld(s.sp + 1), s.st->ld(s.sp + 2));
-      s.gp = mk3(s.st->ld(s.sp + 3), s.st->ld(s.sp + 4), s.st->ld(s.sp + 5));
-      user_warp_vjp<S::kFast>(a0, s.p, theta, gl, s.gp, gtheta);
-#pragma unroll
-      for (int i = 0; i < RM_USER_WARP_MAX_PARAMS; ++i)
-        if (i < a1) padd(s, A + off + i, gtheta[i]);
+      pop_frame(s, s.p, s.gp);
+      user_warp_vjp<S::kFast>(a0, s.p, theta.v, gl, s.gp, theta.g);
+      theta.flush(s, off, a1);
     } break;
 #endif
     default:
@@ -1136,24 +1136,9 @@ struct Scene {
     return s.d;
   }
   RM_DEV float eval(V3 p, bool record = false) const { return eval_near(p, __builtin_nanf(""), record); }
-  // VJP at point p with upstream g: returns dL/dp, adds parameter grads into the accumulators.
-  // `value` (optional) receives f(p) from the recording forward pass.
-  RM_DEV V3 vjp(V3 p, float g, float* value = nullptr) const {
-    Fwd<Store, (RM_FAST_VJP != 0)> f;
-    f.p = p; f.d = 0.0f; f.acc = __builtin_inff(); f.sp = 0; f.tape0 = tape0; f.st = st; f.record = true;
-    f.culled = 0ull; f.lds = lds;
-#pragma unroll
-    for (int k = 0; k < Prog::kTracked; ++k) { f.cull_lo[k] = __builtin_nanf(""); f.cull_hi[k] = __builtin_nanf(""); }
-    prog.forward(f, P);
-    if (value) *value = f.d;
-    Bwd<Store> b;
-    b.p = p; b.gp = mk3(0.0f, 0.0f, 0.0f); b.g = g; b.gframe = 0.0f; b.fval = 0.0f;
-    b.sp = 0; b.tape0 = tape0; b.acc0 = acc0; b.st = st; b.culled = f.culled;
-    prog.backward(b, P);
-    return b.gp;
-  }
-  // dL/dp only (upstream g), no parameter gradients: the accumulator arithmetic is compiled out
-  RM_DEV V3 vjp_point(V3 p, float g, float* value = nullptr) const {
+  // The two halves of a VJP.  The recording forward leaves every fold / onion input on the tape, the skip bits of the culled
+  // children in last_culled and f(p) in `value` (optional); the reverse pass returns dL/dp and, with Acc, accumulates dL/dparams.
+  RM_DEV void record_fwd(V3 p, float* value) const {
     Fwd<Store, (RM_FAST_VJP != 0)> f;
     f.p = p; f.d = 0.0f; f.acc = __builtin_inff(); f.sp = 0; f.tape0 = tape0; f.st = st; f.record = true;
     f.culled = 0ull; f.lds = lds;
@@ -1162,25 +1147,32 @@ struct Scene {
     prog.forward(f, P);
     if (value) *value = f.d;
     last_culled = f.culled;
-    Bwd<Store, false> b;
+  }
+  template <bool Acc> RM_DEV V3 reverse(V3 p, float g) const {
+    Bwd<Store, Acc> b;
     b.p = p; b.gp = mk3(0.0f, 0.0f, 0.0f); b.g = g; b.gframe = 0.0f; b.fval = 0.0f;
-    b.sp = 0; b.tape0 = tape0; b.acc0 = acc0; b.st = st; b.culled = f.culled;
+    b.sp = 0; b.tape0 = tape0; b.acc0 = acc0; b.st = st; b.culled = last_culled;
     prog.backward(b, P);
     return b.gp;
+  }
+  // VJP at point p with upstream g: returns dL/dp, adds parameter grads into the accumulators.
+  // `value` (optional) receives f(p) from the recording forward pass.
+  RM_DEV V3 vjp(V3 p, float g, float* value = nullptr) const {
+    record_fwd(p, value);
+    return reverse<true>(p, g);
+  }
+  // dL/dp only (upstream g), no parameter gradients
+  RM_DEV V3 vjp_point(V3 p, float g, float* value = nullptr) const {
+    record_fwd(p, value);
+    return reverse<false>(p, g);
   }
   // The full VJP (parameter gradients included) at the point of the LAST vjp_point / vjp of this context, without its
   // forward half: the reverse pass only reads the tape slots (fold inputs, onion inputs, the logsumexp value) and the
   // skip bits, and a reverse pass leaves them as they were (its own saves go to the stack region).  No scene
   // evaluation may lie in between.  Used by the converged-tail loop of march_reverse: one point-gradient pass at the
   // anchor, the recursion, then the parameter pass with the summed upstream.
-  mutable unsigned long long last_culled = 0ull;
-  RM_DEV V3 vjp_replay(V3 p, float g) const {
-    Bwd<Store> b;
-    b.p = p; b.gp = mk3(0.0f, 0.0f, 0.0f); b.g = g; b.gframe = 0.0f; b.fval = 0.0f;
-    b.sp = 0; b.tape0 = tape0; b.acc0 = acc0; b.st = st; b.culled = last_culled;
-    prog.backward(b, P);
-    return b.gp;
-  }
+  mutable unsigned long long last_culled = 0ull;   // skip bits of the last recording forward
+  RM_DEV V3 vjp_replay(V3 p, float g) const { return reverse<true>(p, g); }
 };
 
 // --------------------------------------------------------------------------

@@ -996,22 +996,51 @@ RM_DEV void user_probe_values(const SceneT& scene, const ShadeIn& si, const floa
 }
 #endif
 
+// The user shader as the forward of the frame kernels calls it: theta out of the staged block and, for a shader with probes, the
+// scene at its probe points (the one place of the forward that knows about probes); empty in a library without a user shader.
+struct UserShader {
+#ifdef RM_USER_SHADER
+  static constexpr bool kEnabled = true;
+  UserTheta<RM_USER_SHADER_PARAMS> theta;
+  template <class PT> RM_DEV explicit UserShader(const PT& P) : theta(P, RM_USER_SHADER_THETA, RM_USER_SHADER_PARAMS) {}
+#else
+  static constexpr bool kEnabled = false;
+  template <class PT> RM_DEV explicit UserShader(const PT&) {}
+#endif
+#ifdef RM_USER_SHADER_PROBES
+  float d[RM_USER_SHADER_PROBES] = {};
+  template <class SceneT> RM_DEV void probe(const SceneT& scene, const ShadeIn& si) { user_probe_values(scene, si, theta.v, d); }   // in front of fwd
+  RM_DEV V3 fwd(const ShadeIn& si) const { return user_shader_fwd<false>(si, theta.v, d); }
+#else
+  template <class SceneT> RM_DEV void probe(const SceneT&, const ShadeIn&) {}
+#ifdef RM_USER_SHADER
+  RM_DEV V3 fwd(const ShadeIn& si) const { return user_shader_fwd<false>(si, theta.v); }
+#endif
+#endif
+};
+
+// third column of the camera rotation (QuaternionToSO3, quaternion.py:114-124): pixel_frames[..., 2]
+RM_DEV V3 col2_of(const Pose& ps) {
+  const float w = ps.w, x = ps.qv.x, y = ps.qv.y, z = ps.qv.z;
+  return mk3(2.0f * (w * y + x * z), 2.0f * (y * z - w * x), ((w * w - x * x) - y * y) + z * z);
+}
+struct QuatGrad { float w; V3 v; };
+// ... and its VJP: dL/dq from gc = dL/dcol2
+RM_DEV QuatGrad col2_vjp(const Pose& ps, V3 gc) {
+  const float w = ps.w, x = ps.qv.x, y = ps.qv.y, z = ps.qv.z;
+  return QuatGrad{2.0f * ((gc.x * y - gc.y * x) + gc.z * w),
+                  mk3(2.0f * ((gc.x * z - gc.y * w) - gc.z * x), 2.0f * ((gc.x * w + gc.y * z) - gc.z * y),
+                      2.0f * ((gc.x * x + gc.y * y) + gc.z * z))};
+}
+
 // One pixel of Shader.forward (shader.py:190-263).  Modes 1, 2, 5 return the
 // un-normalised value; rm_shade_finish applies the global min/max.
-// `theta` (RM_MODE_USER only): the user shader's parameter floats, copied out of the staged block by the caller.
-// `d` (RM_MODE_USER of a shader with probes only): the scene's values at its probe points.
-#ifdef RM_USER_SHADER_PROBES
-RM_DEV Shaded shade_pixel(int mode, const ShadeIn& s, int cmap_size, int degree, const float* theta = nullptr, const float* d = nullptr) {
-#else
-RM_DEV Shaded shade_pixel(int mode, const ShadeIn& s, int cmap_size, int degree, [[maybe_unused]] const float* theta = nullptr) {
-#endif
+// `us` (RM_MODE_USER only): the user shader with its parameters and probe values, set up by the caller.
+RM_DEV Shaded shade_pixel(int mode, const ShadeIn& s, int cmap_size, int degree, [[maybe_unused]] const UserShader* us = nullptr) {
   switch (mode) {
-#ifdef RM_USER_SHADER_PROBES
+#ifdef RM_USER_SHADER
     case RM_MODE_USER:
-      return plain(user_shader_fwd<false>(s, theta, d));
-#elif defined(RM_USER_SHADER)
-    case RM_MODE_USER:          // (theta: the caller's local array, filled with constant indices, so it dissolves into registers)
-      return plain(user_shader_fwd<false>(s, theta));
+      return plain(us->fwd(s));
 #endif
     case RM_MODE_LAMBERTIAN: {  // shader.py:16-20
       float c = t_clamp(-dot_seq(s.v, s.n), 0.0f, 1.0f);
@@ -1053,6 +1082,106 @@ RM_DEV Shaded shade_pixel(int mode, const ShadeIn& s, int cmap_size, int degree,
       return domain_colour(im, re, cmap_size, degree);   // (imag, real) swapped as in the reference
     }
   }
+}
+
+// VJP of the per-pixel modes of the fused frame (k_render_bwd, kKind 0): dL/d(n, v, q) from the upstream gi3 of the pixel
+RM_DEV ShadeGrad shade_pixel_vjp(const RenderArgs& a, const Pose& ps, V3 v, V3 p, V3 n, V3 gi3) {
+  const V3 z3 = mk3(0.0f, 0.0f, 0.0f);
+  V3 gn = z3, gv = z3;
+  float gq0 = 0.0f, gq1 = 0.0f, gq2 = 0.0f, gq3 = 0.0f;     // direct dependence of the shader on the pose quaternion
+  if (a.mode == RM_MODE_LAMBERTIAN) {
+    float c = -dot_seq(v, n);
+    float g = (c >= 0.0f && c <= 1.0f) ? ((gi3.x + gi3.y) + gi3.z) : 0.0f;   // expand(-1,H,W,3) sums channels
+    gn = mk3(-g * v.x, -g * v.y, -g * v.z);
+    gv = mk3(-g * n.x, -g * n.y, -g * n.z);                                    // direct dependence of the shader on v
+  } else if (a.mode == RM_MODE_NORMAL) {
+    gn = mk3((fabsf(n.x) <= 1.0f) ? gi3.x * sgn0(n.x) : 0.0f,
+             (fabsf(n.y) <= 1.0f) ? gi3.y * sgn0(n.y) : 0.0f,
+             (fabsf(n.z) <= 1.0f) ? gi3.z * sgn0(n.z) : 0.0f);
+  } else if (a.mode == RM_MODE_VIGNETTE) {     // (v . col2(q))^3, shader.py:62-66; col2 = third column of QuaternionToSO3
+    const V3 c2 = col2_of(ps);
+    const float d = dot_seq(v, c2);
+    const float gd = ((gi3.x + gi3.y) + gi3.z) * (3.0f * (d * d));
+    gv = mk3(gd * c2.x, gd * c2.y, gd * c2.z);
+    const QuatGrad gq = col2_vjp(ps, mk3(gd * v.x, gd * v.y, gd * v.z));
+    gq0 = gq.w; gq1 = gq.v.x; gq2 = gq.v.y; gq3 = gq.v.z;
+  } else {   // tangent (6) / spin (7): image = brightness * colormap[index]; the index is piecewise constant
+    ShadeIn si;
+    si.o = p; si.v = v; si.p = p; si.n = n; si.lap = 0.0f; si.dist = 0.0f; si.qw = ps.w; si.qv = ps.qv; si.col2 = v;
+    const Shaded sh = shade_pixel(a.mode, si, a.cmap_size, a.degree);
+    float c0, c1, c2;
+    if (a.cmap_dtype == RM_DTYPE_F64) {
+      const double* c = static_cast<const double*>(a.cmap) + 3 * (int64_t)sh.idx;
+      c0 = (float)c[0]; c1 = (float)c[1]; c2 = (float)c[2];
+    } else {
+      const V3 c = load3_t(a.cmap, sh.idx, a.cmap_dtype);
+      c0 = c.x; c1 = c.y; c2 = c.z;
+    }
+    const float gb = (gi3.x * c0 + gi3.y * c1) + gi3.z * c2;
+    // brightness = (re^2 + im^2).pow(1/2): grad * 0.5 / brightness into the sum of squares, 2 x into each term
+    const float gs = gb * (0.5f / sh.bright);
+    if (a.mode == RM_MODE_TANGENT) {           // shader.py:125-150
+      const float c = dot_seq(n, v);
+      const V3 tg = mk3((c * v.x) * -1.0f + n.x, (c * v.y) * -1.0f + n.y, (c * v.z) * -1.0f + n.z);
+      const V3 u = neg(ps.qv);                 // rotation by conj(q): local = tg + w t + u x t, t = 2 u x tg
+      const V3 pr = qrot(tg, ps.w, u);
+      const V3 gl = mk3(gs * (2.0f * pr.x), gs * (2.0f * pr.y), 0.0f);
+      const V3 t = 2.0f * cross(u, tg);
+      const V3 ugl = cross(u, gl);
+      const V3 gtg = (gl + 2.0f * cross(u, ugl)) - (2.0f * ps.w) * ugl;
+      const V3 gt = ps.w * gl + cross(gl, u);
+      const V3 gu = cross(t, gl) + 2.0f * cross(tg, gt);
+      gq0 = (gl.x * t.x + gl.y * t.y) + gl.z * t.z;
+      gq1 = -gu.x; gq2 = -gu.y; gq3 = -gu.z;
+      const float gtv = dot_seq(gtg, v);       // tg = n - (n.v) v
+      gn = mk3(gtg.x - gtv * v.x, gtg.y - gtv * v.y, gtg.z - gtv * v.z);
+      gv = mk3(-c * gtg.x - gtv * n.x, -c * gtg.y - gtv * n.y, -c * gtg.z - gtv * n.z);
+    } else {                                   // shader.py:157-171: r = (0, n) (x) conj(q)
+      const float q0 = ps.w, q1 = -ps.qv.x, q2 = -ps.qv.y, q3 = -ps.qv.z;
+      const float p1 = n.x, p2 = n.y, p3 = n.z;
+      const float r0 = -((p1 * q1 + p2 * q2) + p3 * q3);
+      const float r1 = (p1 * q0 + p2 * q3) - p3 * q2;
+      const float r2 = (p2 * q0 + p3 * q1) - p1 * q3;
+      const float r3 = (p1 * q2 + p3 * q0) - p2 * q1;
+      const float re = r0 * r0 - ((r1 * r1 + r2 * r2) + r3 * r3);
+      const float nv = norm3(mk3(r1, r2, r3));
+      const float im = (nv * r0) * 2.0f;
+      const float g_im = gs * (2.0f * im), g_re = gs * (2.0f * re);       // domain_colouring(imag, real): both squared alike
+      const float g0 = g_re * (2.0f * r0) + g_im * (2.0f * nv);
+      const float sv = (nv == 0.0f) ? 0.0f : (g_im * (2.0f * r0)) / nv;
+      const float g1 = g_re * (-2.0f * r1) + sv * r1, g2 = g_re * (-2.0f * r2) + sv * r2, g3 = g_re * (-2.0f * r3) + sv * r3;
+      gn = mk3(((-q1 * g0 + q0 * g1) - q3 * g2) + q2 * g3, ((-q2 * g0 + q3 * g1) + q0 * g2) - q1 * g3,
+               ((-q3 * g0 - q2 * g1) + q1 * g2) + q0 * g3);
+      const float gc0 = (p1 * g1 + p2 * g2) + p3 * g3;
+      const float gc1 = (-p1 * g0 + p3 * g2) - p2 * g3;
+      const float gc2 = (-p2 * g0 - p3 * g1) + p1 * g3;
+      const float gc3 = (-p3 * g0 + p2 * g1) - p1 * g2;
+      gq0 = gc0; gq1 = -gc1; gq2 = -gc2; gq3 = -gc3;
+    }
+  }
+  return ShadeGrad{z3, gv, z3, gn, z3, gq0, mk3(gq1, gq2, gq3)};
+}
+// ... of the distance shader (kKind 3), norm(o - p).clamp(1e-2, inf).log(): dL/do = -dL/dp, g / clamped along (o - p) / norm
+RM_DEV V3 distance_vjp(V3 o, V3 p, float g) {
+  const V3 d = o - p;
+  const float dn = norm3(d);
+  const float gd = (dn >= 1e-2f) ? g / dn : 0.0f;
+  return (dn == 0.0f) ? mk3(0.0f, 0.0f, 0.0f) : mk3(gd * (d.x / dn), gd * (d.y / dn), gd * (d.z / dn));
+}
+// The normal these VJPs start from: from the un-normalised normal u the recording forward left (same division, same bits), or
+// -- callers without that buffer -- from four tap evaluations
+template <class SceneT>
+RM_DEV V3 shading_normal(const RenderArgs& a, const SceneT& scene, const Tetra& T, V3 p, int64_t li, V3& u) {
+  V3 n;
+  if (a.normal_u) {
+    u = load3(a.normal_u, li);
+    const float nu = norm3(u);
+    n = mk3(u.x / nu, u.y / nu, u.z / nu);
+  } else {
+    float lap;
+    normals_forward(scene, T, p, 0.0f, n, lap, &u);
+  }
+  return n;
 }
 
 // fold a wave's running min/max (+NaN flag) into one of the workspace's partial triples (include/rm_abi.h): every
@@ -1196,28 +1325,11 @@ RM_DEV void finish_tile(const RenderArgs& a, const SceneT& scene, const Tetra& T
   }
   ShadeIn si;
   si.o = r.o; si.v = r.v; si.p = p; si.n = n; si.lap = lap; si.dist = dist;
-  si.qw = r.ps.w; si.qv = r.ps.qv;
-  {   // third column of the camera rotation (QuaternionToSO3, quaternion.py:114-124)
-    float w = r.ps.w, x = r.ps.qv.x, y = r.ps.qv.y, z = r.ps.qv.z;
-    si.col2 = mk3(2.0f * (w * y + x * z), 2.0f * (y * z - w * x), ((w * w - x * x) - y * y) + z * z);
-  }
-#ifdef RM_USER_SHADER
-  if (mode == RM_MODE_USER) si.lap = 0.0f;      // (the taps' sum without the centre value is no Laplacian: a user shader reads 0)
-  // theta out of the staged block into a local array, as RM_OP_USER does: constant indices, so it dissolves into the registers
-  // the block lives in
-  float theta[RM_USER_SHADER_PARAMS > 0 ? RM_USER_SHADER_PARAMS : 1] = {};
-#pragma unroll
-  for (int i = 0; i < RM_USER_SHADER_PARAMS; ++i) theta[i] = scene.P[RM_USER_SHADER_THETA + i];
-#ifdef RM_USER_SHADER_PROBES
-  float d[RM_USER_SHADER_PROBES] = {};
-  if (mode == RM_MODE_USER) user_probe_values(scene, si, theta, d);      // (mode is uniform: every lane of the wave evaluates)
-  const Shaded sh = shade_pixel(mode, si, a.cmap_size, a.degree, theta, d);
-#else
-  const Shaded sh = shade_pixel(mode, si, a.cmap_size, a.degree, theta);
-#endif
-#else
-  const Shaded sh = shade_pixel(mode, si, a.cmap_size, a.degree);
-#endif
+  si.qw = r.ps.w; si.qv = r.ps.qv; si.col2 = col2_of(r.ps);
+  if (UserShader::kEnabled && mode == RM_MODE_USER) si.lap = 0.0f;       // (the taps' sum without the centre value is no Laplacian: a user shader reads 0)
+  UserShader us(scene.P);
+  if (UserShader::kEnabled && mode == RM_MODE_USER) us.probe(scene, si);   // (mode is uniform: every lane of the wave evaluates)
+  const Shaded sh = shade_pixel(mode, si, a.cmap_size, a.degree, &us);
   const V3 out = sh.rgb;
   const bool global = (mode == RM_MODE_DISTANCE || mode == RM_MODE_PROXIMITY || mode == RM_MODE_LAPLACIAN);
   if (r.live) {
@@ -2051,17 +2163,8 @@ __global__ void __launch_bounds__(256) RM_BWD_OCC k_render_bwd(RenderArgs a) {
     V3 v = qrot(load3(static_cast<const float*>(a.cam.ray_directions), gi), ps.w, ps.qv);
     V3 p = load3(a.p_final, li);
     V3 gi3 = live ? load3(a.grad_image, li) : mk3(0.0f, 0.0f, 0.0f);
-    // the normal for the shader VJP: from the un-normalised normal the recording forward left (same division, same
-    // bits), or -- callers without that buffer -- from four tap evaluations
-    V3 n, u = mk3(0.0f, 0.0f, 0.0f);
-    if (a.normal_u) {
-      u = load3(a.normal_u, li);
-      const float nu = norm3(u);
-      n = mk3(u.x / nu, u.y / nu, u.z / nu);
-    } else {
-      float lap;
-      normals_forward(scene, T, p, 0.0f, n, lap, &u);
-    }
+    V3 u = mk3(0.0f, 0.0f, 0.0f);
+    const V3 n = shading_normal(a, scene, T, p, li, u);
     V3 gn = mk3(0.0f, 0.0f, 0.0f);
     V3 gv = mk3(0.0f, 0.0f, 0.0f);
     float gq0 = 0.0f, gq1 = 0.0f, gq2 = 0.0f, gq3 = 0.0f;     // direct dependence of the shader on the pose quaternion
@@ -2072,19 +2175,16 @@ __global__ void __launch_bounds__(256) RM_BWD_OCC k_render_bwd(RenderArgs a) {
       // every lane gets here (a lane without a ray runs on ray 0 with a zero upstream): the accumulator rows sum over the wave
       ShadeIn si;
       si.o = qrot(load3(static_cast<const float*>(a.cam.ray_positions), gi), ps.w, ps.qv) + ps.t;
-      si.v = v; si.p = p; si.n = n; si.lap = 0.0f; si.dist = 0.0f; si.qw = ps.w; si.qv = ps.qv;
-      const float w = ps.w, x = ps.qv.x, y = ps.qv.y, z = ps.qv.z;
-      si.col2 = mk3(2.0f * (w * y + x * z), 2.0f * (y * z - w * x), ((w * w - x * x) - y * y) + z * z);
+      si.v = v; si.p = p; si.n = n; si.lap = 0.0f; si.dist = 0.0f; si.qw = ps.w; si.qv = ps.qv; si.col2 = col2_of(ps);
       float theta[RM_USER_SHADER_PARAMS > 0 ? RM_USER_SHADER_PARAMS : 1] = {}, gtheta[RM_USER_SHADER_PARAMS > 0 ? RM_USER_SHADER_PARAMS : 1] = {};
 #pragma unroll
       for (int i = 0; i < RM_USER_SHADER_PARAMS; ++i) theta[i] = scene.P[RM_USER_SHADER_THETA + i];
       const V3 z3 = mk3(0.0f, 0.0f, 0.0f);
       ShadeGrad gs{z3, z3, z3, z3, z3, 0.0f, z3};
 #ifdef RM_USER_SHADER_PROBES
-      // the probe values again (K evaluations: the recording forward writes no buffer for them), the shader's VJP, which also
-      // hands back dL/dd[k], then per probe the scene's VJP at the probe point -- its parameter gradients go where the taps' go,
-      // complete before the reverse march starts -- and the probe's own VJP, which adds to gs and gtheta.  Every lane reaches every
-      // scene.vjp, a lane without a ray with a zero upstream.  Both loops rolled; d / gd indexed by constants only.
+      // the probe values again (K evaluations: the recording forward writes no buffer for them), the shader's VJP, which also hands
+      // back dL/dd[k], then per probe the scene's VJP at the probe point (its parameter gradients go where the taps' go) and the
+      // probe's own VJP, which adds to gs and gtheta.  Every lane reaches every scene.vjp; both loops rolled, d / gd indexed by constants.
       float d[RM_USER_SHADER_PROBES] = {}, gd[RM_USER_SHADER_PROBES] = {};
       user_probe_values(scene, si, theta, d);
       user_shader_vjp<(RM_FAST_VJP != 0)>(si, theta, d, gi3, gs, gtheta, gd);
@@ -2100,95 +2200,15 @@ __global__ void __launch_bounds__(256) RM_BWD_OCC k_render_bwd(RenderArgs a) {
 #pragma unroll
       for (int i = 0; i < RM_USER_SHADER_PARAMS; ++i) scene.st->add(scene.acc0 + RM_USER_SHADER_THETA + i, live ? gtheta[i] : 0.0f);
       gn = gs.n; gv = gs.v; gp_direct = gs.o; gp_surface = gs.p;
-      const V3 gc = gs.col2;      // col2(q) = third column of QuaternionToSO3: the vignette's four lines, plus the direct terms
-      gq0 = 2.0f * ((gc.x * y - gc.y * x) + gc.z * w) + gs.qw;
-      gq1 = 2.0f * ((gc.x * z - gc.y * w) - gc.z * x) + gs.qv.x;
-      gq2 = 2.0f * ((gc.x * w + gc.y * z) - gc.z * y) + gs.qv.y;
-      gq3 = 2.0f * ((gc.x * x + gc.y * y) + gc.z * z) + gs.qv.z;
+      const QuatGrad gq = col2_vjp(ps, gs.col2);      // col2(q): the vignette's chain, plus the direct terms
+      gq0 = gq.w + gs.qw; gq1 = gq.v.x + gs.qv.x; gq2 = gq.v.y + gs.qv.y; gq3 = gq.v.z + gs.qv.z;
 #endif
     } else if constexpr (kKind == 3) {
-      // norm(origin - p).clamp(1e-2, inf).log(): grad / clamped, masked by the clamp, along (origin - p) / norm
-      const V3 o = qrot(load3(static_cast<const float*>(a.cam.ray_positions), gi), ps.w, ps.qv) + ps.t;
-      const V3 d = o - p;
-      const float dn = norm3(d);
-      const float gd = (dn >= 1e-2f) ? gi3.x / dn : 0.0f;
-      gp_direct = (dn == 0.0f) ? mk3(0.0f, 0.0f, 0.0f) : mk3(gd * (d.x / dn), gd * (d.y / dn), gd * (d.z / dn));
-    } else if constexpr (kKind != 0) {
-      // nothing here: the upstream of these modes is on the Laplacian / on scene(p), not on the normal (below)
-    } else if (a.mode == RM_MODE_LAMBERTIAN) {
-      float c = -dot_seq(v, n);
-      float g = (c >= 0.0f && c <= 1.0f) ? ((gi3.x + gi3.y) + gi3.z) : 0.0f;   // expand(-1,H,W,3) sums channels
-      gn = mk3(-g * v.x, -g * v.y, -g * v.z);
-      gv = mk3(-g * n.x, -g * n.y, -g * n.z);                                    // direct dependence of the shader on v
-    } else if (a.mode == RM_MODE_NORMAL) {
-      gn = mk3((fabsf(n.x) <= 1.0f) ? gi3.x * sgn0(n.x) : 0.0f,
-               (fabsf(n.y) <= 1.0f) ? gi3.y * sgn0(n.y) : 0.0f,
-               (fabsf(n.z) <= 1.0f) ? gi3.z * sgn0(n.z) : 0.0f);
-    } else if (a.mode == RM_MODE_VIGNETTE) {     // (v . col2(q))^3, shader.py:62-66; col2 = third column of QuaternionToSO3
-      const float w = ps.w, x = ps.qv.x, y = ps.qv.y, z = ps.qv.z;
-      const V3 c2 = mk3(2.0f * (w * y + x * z), 2.0f * (y * z - w * x), ((w * w - x * x) - y * y) + z * z);
-      const float d = dot_seq(v, c2);
-      const float gd = ((gi3.x + gi3.y) + gi3.z) * (3.0f * (d * d));
-      gv = mk3(gd * c2.x, gd * c2.y, gd * c2.z);
-      const V3 gc = mk3(gd * v.x, gd * v.y, gd * v.z);
-      gq0 = 2.0f * ((gc.x * y - gc.y * x) + gc.z * w);
-      gq1 = 2.0f * ((gc.x * z - gc.y * w) - gc.z * x);
-      gq2 = 2.0f * ((gc.x * w + gc.y * z) - gc.z * y);
-      gq3 = 2.0f * ((gc.x * x + gc.y * y) + gc.z * z);
-    } else {   // tangent (6) / spin (7): image = brightness * colormap[index]; the index is piecewise constant
-      ShadeIn si;
-      si.o = p; si.v = v; si.p = p; si.n = n; si.lap = 0.0f; si.dist = 0.0f; si.qw = ps.w; si.qv = ps.qv; si.col2 = v;
-      const Shaded sh = shade_pixel(a.mode, si, a.cmap_size, a.degree);
-      float c0, c1, c2;
-      if (a.cmap_dtype == RM_DTYPE_F64) {
-        const double* c = static_cast<const double*>(a.cmap) + 3 * (int64_t)sh.idx;
-        c0 = (float)c[0]; c1 = (float)c[1]; c2 = (float)c[2];
-      } else {
-        const V3 c = load3_t(a.cmap, sh.idx, a.cmap_dtype);
-        c0 = c.x; c1 = c.y; c2 = c.z;
-      }
-      const float gb = (gi3.x * c0 + gi3.y * c1) + gi3.z * c2;
-      // brightness = (re^2 + im^2).pow(1/2): grad * 0.5 / brightness into the sum of squares, 2 x into each term
-      const float gs = gb * (0.5f / sh.bright);
-      if (a.mode == RM_MODE_TANGENT) {           // shader.py:125-150
-        const float c = dot_seq(n, v);
-        const V3 tg = mk3((c * v.x) * -1.0f + n.x, (c * v.y) * -1.0f + n.y, (c * v.z) * -1.0f + n.z);
-        const V3 u = neg(ps.qv);                 // rotation by conj(q): local = tg + w t + u x t, t = 2 u x tg
-        const V3 pr = qrot(tg, ps.w, u);
-        const V3 gl = mk3(gs * (2.0f * pr.x), gs * (2.0f * pr.y), 0.0f);
-        const V3 t = 2.0f * cross(u, tg);
-        const V3 ugl = cross(u, gl);
-        const V3 gtg = (gl + 2.0f * cross(u, ugl)) - (2.0f * ps.w) * ugl;
-        const V3 gt = ps.w * gl + cross(gl, u);
-        const V3 gu = cross(t, gl) + 2.0f * cross(tg, gt);
-        gq0 = (gl.x * t.x + gl.y * t.y) + gl.z * t.z;
-        gq1 = -gu.x; gq2 = -gu.y; gq3 = -gu.z;
-        const float gtv = dot_seq(gtg, v);       // tg = n - (n.v) v
-        gn = mk3(gtg.x - gtv * v.x, gtg.y - gtv * v.y, gtg.z - gtv * v.z);
-        gv = mk3(-c * gtg.x - gtv * n.x, -c * gtg.y - gtv * n.y, -c * gtg.z - gtv * n.z);
-      } else {                                   // shader.py:157-171: r = (0, n) (x) conj(q)
-        const float q0 = ps.w, q1 = -ps.qv.x, q2 = -ps.qv.y, q3 = -ps.qv.z;
-        const float p1 = n.x, p2 = n.y, p3 = n.z;
-        const float r0 = -((p1 * q1 + p2 * q2) + p3 * q3);
-        const float r1 = (p1 * q0 + p2 * q3) - p3 * q2;
-        const float r2 = (p2 * q0 + p3 * q1) - p1 * q3;
-        const float r3 = (p1 * q2 + p3 * q0) - p2 * q1;
-        const float re = r0 * r0 - ((r1 * r1 + r2 * r2) + r3 * r3);
-        const float nv = norm3(mk3(r1, r2, r3));
-        const float im = (nv * r0) * 2.0f;
-        const float g_im = gs * (2.0f * im), g_re = gs * (2.0f * re);       // domain_colouring(imag, real): both squared alike
-        const float g0 = g_re * (2.0f * r0) + g_im * (2.0f * nv);
-        const float sv = (nv == 0.0f) ? 0.0f : (g_im * (2.0f * r0)) / nv;
-        const float g1 = g_re * (-2.0f * r1) + sv * r1, g2 = g_re * (-2.0f * r2) + sv * r2, g3 = g_re * (-2.0f * r3) + sv * r3;
-        gn = mk3(((-q1 * g0 + q0 * g1) - q3 * g2) + q2 * g3, ((-q2 * g0 + q3 * g1) + q0 * g2) - q1 * g3,
-                 ((-q3 * g0 - q2 * g1) + q1 * g2) + q0 * g3);
-        const float gc0 = (p1 * g1 + p2 * g2) + p3 * g3;
-        const float gc1 = (-p1 * g0 + p3 * g2) - p2 * g3;
-        const float gc2 = (-p2 * g0 - p3 * g1) + p1 * g3;
-        const float gc3 = (-p3 * g0 + p2 * g1) - p1 * g2;
-        gq0 = gc0; gq1 = -gc1; gq2 = -gc2; gq3 = -gc3;
-      }
-    }
+      gp_direct = distance_vjp(qrot(load3(static_cast<const float*>(a.cam.ray_positions), gi), ps.w, ps.qv) + ps.t, p, gi3.x);
+    } else if constexpr (kKind == 0) {
+      const ShadeGrad gs = shade_pixel_vjp(a, ps, v, p, n, gi3);
+      gn = gs.n; gv = gs.v; gq0 = gs.qw; gq1 = gs.qv.x; gq2 = gs.qv.y; gq3 = gs.qv.z;
+    }   // (kinds 1 and 2: the upstream of these modes is on the Laplacian / on scene(p), not on the normal: below)
     if (live && a.grad_qdir) {
       float* gq = a.grad_qdir + 4 * li;
       gq[0] = gq0; gq[1] = gq1; gq[2] = gq2; gq[3] = gq3;
@@ -2369,12 +2389,9 @@ __global__ void k_bwd_hard_a(RenderArgs a) {
     const float sumf = ((dp.x * v.x + dp.y * v.y) + dp.z * v.z) / ((v.x * v.x + v.y * v.y) + v.z * v.z);
     gv = gv + sumf * lam;
   }
-  // (distance shader: k_render_bwd left the shader's direct dependence on the origin there for the deferred rays)
-#ifdef RM_USER_SHADER     // (... and so did a user shader)
-  if (valid && a.grad_pos) store3(a.grad_pos, li, (a.mode == RM_MODE_DISTANCE || a.mode == RM_MODE_USER) ? lam + load3(a.grad_pos, li) : lam);
-#else
-  if (valid && a.grad_pos) store3(a.grad_pos, li, a.mode == RM_MODE_DISTANCE ? lam + load3(a.grad_pos, li) : lam);
-#endif
+  // (distance shader, user shader: k_render_bwd left the shader's direct dependence on the origin there for the deferred rays)
+  const bool direct = a.mode == RM_MODE_DISTANCE || (UserShader::kEnabled && a.mode == RM_MODE_USER);
+  if (valid && a.grad_pos) store3(a.grad_pos, li, direct ? lam + load3(a.grad_pos, li) : lam);
   if (valid && a.grad_dirs) store3(a.grad_dirs, li, gv);
 }
 
