@@ -2229,7 +2229,11 @@ __global__ void __launch_bounds__(256) RM_BWD_OCC k_render_bwd(RenderArgs a) {
       }
       RM_STAMP(stamps, 1);
       int ne = a.nexec ? a.nexec[li] : a.steps;
-      const int64_t tslot = tc.tile * 64 + (threadIdx.x & 63);
+      // A lane without a pixel runs as ray 0 with a zero upstream: on ray 0's trajectory (slot 0 = tile 0, lane 0), since the
+      // forward never wrote the lane's own slot (0 x whatever that memory holds went into the accumulators), and with lambda
+      // exactly 0, so that a NaN ray 0 does not make the lane an active ray that is deferred as a second ray 0.
+      const int64_t tslot = live ? tc.tile * 64 + (threadIdx.x & 63) : 0;
+      if (!live) lam = mk3(0.0f, 0.0f, 0.0f);
       lam = march_reverse<decltype(scene), DeferToList, true>(scene, lam, v, p, a.traj, a.steps, tslot, ne, a.steps,
                                                               a.grad_dirs != nullptr, gv, a.flags & RM_FLAG_EARLY_OUT, &walked,
                                                               DeferToList{a, li, tslot}, &deferred, stamps);
