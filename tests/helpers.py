@@ -107,6 +107,101 @@ def ulp_distance(got, want):
     return (ordered(got) - ordered(want)).abs()
 
 
+# --------------------------------------------------------------------------
+# the rule of tests/test_fast_build.py: the precision="fast" build against the float64 oracle
+# --------------------------------------------------------------------------
+# E_fast = |fast - o64| must stay within FAST_FACTOR times E_ref = |o32 - o64|, the oracle's own float32 error on the same
+# inputs, plus a floor of float32 resolution.  The factor is derived, not fitted: every operation the fast build swaps in is
+# documented in csrc/rm_device.h as <= ~2 ulp (v_exp_f32 / v_log_f32), 1 ulp (v_sqrt_f32) or 1.5 ulp (v_rcp_f32 and a
+# multiply) where the correctly rounded forms they replace have 0.5 ulp; FMA contraction only removes roundings.
+FAST_FACTOR = 4.0
+FAST_RATIOS = {}      # group -> (largest E_fast / E_ref seen, where), printed by fast_note as it grows
+
+
+def fast_note(group, ratio, what):
+    if ratio > FAST_RATIOS.get(group, (-1.0, ""))[0]:
+        FAST_RATIOS[group] = (ratio, what)
+    print(f"fast build [{group}]: largest E_fast / E_ref so far {FAST_RATIOS[group][0]:.3g} ({FAST_RATIOS[group][1]})")
+
+
+def _ratio(fast, ref, floor):
+    """E_fast / E_ref for the record; where the reference's own error is below the floor, against the floor."""
+    return fast / max(ref, floor) if max(ref, floor) > 0.0 else (0.0 if fast == 0.0 else float("inf"))
+
+
+def fast_errors(what, got, o32, o64):
+    """(E_fast, E_ref, valid) as float64 CPU tensors.  NaN positions of ``got`` must equal the reference's wherever o32 and
+    o64 agree on them; ``valid`` marks the elements finite in both, where the two errors are defined."""
+    got, o32, o64 = (torch.as_tensor(x).detach().double().cpu() for x in (got, o32, o64))
+    assert got.shape == o32.shape == o64.shape, (what, got.shape, o32.shape, o64.shape)
+    agree = torch.isnan(o32) == torch.isnan(o64)
+    bad = (torch.isnan(got) != torch.isnan(o64)) & agree
+    assert not bool(bad.any()), f"{what}: NaN at {int(torch.isnan(got).sum())} positions, the reference at " \
+                                f"{int(torch.isnan(o64).sum())}; {int(bad.sum())} positions differ"
+    valid = ~torch.isnan(o32) & ~torch.isnan(o64)
+    zero = torch.zeros_like(o64)
+    return torch.where(valid, (got - o64).abs(), zero), torch.where(valid, (o32 - o64).abs(), zero), valid
+
+
+def fast_value_rule(group, what, got, o32, o64, factor=FAST_FACTOR):
+    """max E_fast <= max(factor max E_ref, u) and mean E_fast <= max(factor mean E_ref, u / 4) with u = 2^-23 max|o64|
+    (E_ref is exactly 0 for a plane).  Prints every figure before it asserts; -> the larger of the two ratios."""
+    e_fast, e_ref, valid = fast_errors(what, got, o32, o64)
+    assert bool(valid.any()), what
+    u = 2.0 ** -23 * float(torch.as_tensor(o64).detach().double().cpu()[valid].abs().max())
+    mx_f, mx_r = float(e_fast[valid].max()), float(e_ref[valid].max())
+    mn_f, mn_r = float(e_fast[valid].mean()), float(e_ref[valid].mean())
+    ratio = max(_ratio(mx_f, mx_r, u), _ratio(mn_f, mn_r, u / 4))
+    print(f"{what}: max E_fast {mx_f:.3g} E_ref {mx_r:.3g} (ratio {_ratio(mx_f, mx_r, u):.3g}), mean E_fast {mn_f:.3g} "
+          f"E_ref {mn_r:.3g} (ratio {_ratio(mn_f, mn_r, u / 4):.3g}), u {u:.3g}")
+    fast_note(group, ratio, what)
+    assert mx_f <= max(factor * mx_r, u), (what, mx_f, mx_r, u)
+    assert mn_f <= max(factor * mn_r, u / 4), (what, mn_f, mn_r, u)
+    return ratio
+
+
+def fast_frame_rule(group, what, got, o32, o64, factor=FAST_FACTOR):
+    """Frames [N, H, W, 3], per-pixel error e = max over the channels:  q90(e_fast) <= max(factor q90(e_ref), 2^-22),  at most
+    1 % of the pixels with e_fast > 1e-3 (so that no block of wrong pixels hides behind the quantile), and NaN positions
+    equal to the reference's wherever o32 and o64 agree on them.  Prints every figure before it asserts; -> the q90 ratio."""
+    e_fast, e_ref, valid = fast_errors(what, got, o32, o64)
+    pixel = valid.all(dim=-1)
+    assert bool(pixel.any()), what
+    e_fast, e_ref = e_fast.amax(dim=-1)[pixel], e_ref.amax(dim=-1)[pixel]
+    q_f, q_r = float(torch.quantile(e_fast, 0.9)), float(torch.quantile(e_ref, 0.9))
+    share_f, share_r = float((e_fast > 1e-3).double().mean()), float((e_ref > 1e-3).double().mean())
+    ratio = _ratio(q_f, q_r, 2.0 ** -22)
+    print(f"{what}: q90 e_fast {q_f:.3g} e_ref {q_r:.3g} (ratio {ratio:.3g}), max e_fast {float(e_fast.max()):.3g} e_ref "
+          f"{float(e_ref.max()):.3g}, share beyond 1e-3 fast {share_f:.3g} ref {share_r:.3g}, {int(pixel.sum())} of {pixel.numel()} pixels")
+    fast_note(group, ratio, what)
+    assert q_f <= max(factor * q_r, 2.0 ** -22), (what, q_f, q_r)
+    assert share_f <= 0.01, (what, share_f)
+    return ratio
+
+
+def fast_gradient_rule(group, what, got, g32, g64, factor=FAST_FACTOR):
+    """One gradient tensor:  max|got - g64| <= max(1e-4 max(1, |g64|max), factor max|g32 - g64|)  -- the project's gradient
+    contract, or the rule above -- and a NaN pattern equal to the float64 reference's, element for element.  Prints every
+    figure before it asserts; -> max|got - g64| / max|g32 - g64|."""
+    got, g32, g64 = (torch.as_tensor(x).detach().double().cpu() for x in (got, g32, g64))
+    assert got.shape == g32.shape == g64.shape, (what, got.shape, g32.shape, g64.shape)
+    print(f"{what}: NaN at {int(torch.isnan(got).sum())} of {got.numel()} elements, g64 at {int(torch.isnan(g64).sum())}, "
+          f"g32 at {int(torch.isnan(g32).sum())}")
+    assert torch.equal(torch.isnan(got), torch.isnan(g64)), (what, got, g64)
+    fin = ~torch.isnan(g64)
+    if not bool(fin.any()):
+        return 0.0
+    both = fin & ~torch.isnan(g32)
+    spread = float((g32 - g64)[both].abs().max()) if bool(both.any()) else 0.0
+    scale = max(1.0, float(g64[fin].abs().max()))
+    err = float((got - g64)[fin].abs().max())
+    ratio = _ratio(err, spread, 2.0 ** -23 * scale)
+    print(f"{what}: |got - g64| {err:.3g}, |g32 - g64| {spread:.3g} (ratio {ratio:.3g}), |g64|max {scale:.3g}")
+    fast_note(group, ratio, what)
+    assert err <= max(1e-4 * scale, factor * spread), (what, err, spread, scale)
+    return ratio
+
+
 def random_spec(gen, depth=0, max_depth=4):
     """Random SDF tree over all 11 node types (oracle spec); `gen` is a torch.Generator."""
     def u(lo, hi, n=None):
