@@ -37,7 +37,10 @@ from ray_marching_amd.scene.scene_registry import make_test_scene2  # noqa: E402
 PX, EPS = 3.45e-6, 5e-2
 MODES = {"directional": lambda: contrib.DirectionalLightShader([0.35, 0.5, -0.8], [0.9, 0.55, 0.3], 0.15),
          "ambient_occlusion": lambda: contrib.AmbientOcclusionShader(0.4, 2.0, [0.9, 0.6, 0.4]),
-         "soft_shadow": lambda: contrib.SoftShadowShader([0.35, 0.5, -0.8], [0.9, 0.55, 0.3], 0.15, 2.0, 2.0, 0.02)}
+         "soft_shadow": lambda: contrib.SoftShadowShader([0.35, 0.5, -0.8], [0.9, 0.55, 0.3], 0.15, 2.0, 2.0, 0.02),
+         # K = 8 chained probes (the same eight evaluations as soft_shadow, placed by the march):
+         #     python profiles/user_shader_probes_ab.py --which soft_shadow,marched_shadow > profiles/user_shader_chained_probes_ab.txt
+         "marched_shadow": lambda: contrib.MarchedShadowShader([0.35, 0.5, -0.8], [0.9, 0.55, 0.3], 0.15, 2.0, 0.1, 0.02, 0.02, 0.5)}
 
 
 def loop_for(scene, h, w, dev):

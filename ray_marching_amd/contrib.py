@@ -668,7 +668,8 @@ class SoftShadowShader(nn.Module):
     only between clamped values (0 or 1), whose gradient is zero on both sides, so which of them is picked does not matter.
     ``bias`` is a constructor constant, not a trainable parameter: it is kept as a frozen ``nn.Parameter`` (``requires_grad =
     False``) only so that its value travels in ``theta`` like the others; it receives no gradient.  The steps are fixed: a
-    marched shadow ray, whose next point depends on the last distance, is not what probes can say (extensions.py).
+    marched shadow ray, whose next point depends on the last distance, is what MarchedShadowShader below does with chained
+    probes (extensions.py).
 
     ``scene``: a callable ``points[..., 3] -> [..., 1]``."""
 
@@ -782,3 +783,148 @@ template <bool Fast> RM_DEV void soft_shadow_vjp(const rm::ShadeIn& s, const flo
 
 register_shader(SoftShadowShader, params=("light_direction", "albedo", "ambient", "sharpness", "reach", "bias"), hip=_SOFT_SHADOW_HIP,
                 probes=8)
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# Shaders whose probes form a chain (register_shader(probes=K, chained=True)): each probe is placed from the values before it
+# --------------------------------------------------------------------------------------------------------------------
+class MarchedShadowShader(nn.Module):
+    """A distant light with a sphere-traced penumbra shadow: eight probes marched from ``o = p + bias n`` towards the light ``l`` (the
+    normalised ``light_direction``), ``t_0 = start``, ``q_k = o + t_k l``, ``d_k = scene(q_k)``, ``t_{k+1} = t_k + clamp(d_k, step_min,
+    step_max)``; ``shadow = min_k clamp(sharpness d_k / t_k, 0, 1)`` and ``rgb = albedo * (ambient + (1 - ambient) * clamp(n . l, 0, 1) *
+    shadow)``.  The same eight evaluations as SoftShadowShader, spent where the scene says: small steps next to an occluder,
+    ``step_max`` in the open.  Nine trainable floats (``light_direction`` [3], ``albedo`` [3], ``ambient``, ``sharpness``, ``start``).
+
+    The gradient of the minimum goes to the first minimal index, as in SoftShadowShader; both clamps pass their gradient on the
+    closed interval.  ``bias``, ``step_min`` and ``step_max`` are constructor constants kept as frozen ``nn.Parameter``s
+    (``requires_grad = False``) so that their values travel in ``theta``; they receive no gradient.
+
+    ``scene``: a callable ``points[..., 3] -> [..., 1]``."""
+
+    def __init__(self, light_direction=(0.0, 0.0, -1.0), albedo=(1.0, 1.0, 1.0), ambient: float = 0.15, sharpness: float = 8.0,
+                 start: float = 0.1, bias: float = 0.02, step_min: float = 0.02, step_max: float = 0.5) -> None:
+        super().__init__()
+        self.light_direction = nn.Parameter(torch.tensor(light_direction, dtype=torch.float32))
+        self.albedo = nn.Parameter(torch.tensor(albedo, dtype=torch.float32))
+        self.ambient = nn.Parameter(torch.tensor(ambient, dtype=torch.float32))
+        self.sharpness = nn.Parameter(torch.tensor(sharpness, dtype=torch.float32))
+        self.start = nn.Parameter(torch.tensor(start, dtype=torch.float32))
+        self.bias = nn.Parameter(torch.tensor(bias, dtype=torch.float32), requires_grad=False)
+        self.step_min = nn.Parameter(torch.tensor(step_min, dtype=torch.float32), requires_grad=False)
+        self.step_max = nn.Parameter(torch.tensor(step_max, dtype=torch.float32), requires_grad=False)
+
+    def forward(self, px_coords: Tensor, camera_orientation: Tensor, pixel_frames: Tensor, ray_directions: Tensor,
+                surface_coords: Tensor, surface_normals: Tensor, scene) -> Tensor:
+        light = self.light_direction / torch.linalg.vector_norm(self.light_direction)
+        origin = surface_coords + self.bias * surface_normals
+        t = self.start
+        steps = []
+        for k in range(8):
+            d = scene(origin + t * light)
+            steps.append((self.sharpness * d / t).clamp(0, 1))
+            if k < 7:
+                t = t + d.clamp(self.step_min, self.step_max)
+        shadow = torch.cat(steps, dim=-1).min(dim=-1, keepdim=True).values
+        c = (surface_normals * light).sum(dim=-1, keepdim=True).clamp(0, 1)
+        return self.albedo * (self.ambient + (1 - self.ambient) * c * shadow)
+
+
+# theta = {light_direction[3], albedo[3], ambient, sharpness, start, bias, step_min, step_max}.  The probe pair sees the chain as the
+# history h[i] = d_{k-1-i} (0 behind the start of the chain) and k as a run-time value: t_k = ((start + c_0) + c_1) + ... in the
+# order the PyTorch forward adds them, oldest first, i.e. h from its far end -- the entries behind the start are masked by
+# `i < k` (clamp(0, step_min, step_max) is step_min, not 0), and adding their 0.0f leaves `start` as it is.  NAME_fwd / NAME_vjp see
+# d in probe order and rebuild the t_k the same way; the VJP of the minimum hands the winner's dL/dt_j back to d_0 .. d_{j-1}.
+_MARCHED_SHADOW_HIP = r"""
+template <bool Fast> RM_DEV rm::V3 marched_shadow_probe(int k, const rm::ShadeIn& s, const float* theta, const float* h) {
+  const rm::V3 L = mk3(theta[0], theta[1], theta[2]);
+  const float ln = norm3(L);
+  const rm::V3 l = mk3(L.x / ln, L.y / ln, L.z / ln);
+  float t = theta[8];
+#pragma unroll
+  for (int i = 6; i >= 0; --i) t = t + ((i < k) ? t_clamp(h[i], theta[10], theta[11]) : 0.0f);
+  return mk3((s.p.x + theta[9] * s.n.x) + t * l.x, (s.p.y + theta[9] * s.n.y) + t * l.y, (s.p.z + theta[9] * s.n.z) + t * l.z);
+}
+template <bool Fast> RM_DEV void marched_shadow_probe_vjp(int k, const rm::ShadeIn& s, const float* theta, const float* h, rm::V3 gq,
+                                                          rm::ShadeGrad& gs, float* gtheta, float* gh) {
+  const rm::V3 L = mk3(theta[0], theta[1], theta[2]);
+  const float ln = norm3_t<Fast>(L);
+  const rm::V3 l = mk3(div_t<Fast>(L.x, ln), div_t<Fast>(L.y, ln), div_t<Fast>(L.z, ln));
+  float t = theta[8];
+#pragma unroll
+  for (int i = 6; i >= 0; --i) t = t + ((i < k) ? t_clamp(h[i], theta[10], theta[11]) : 0.0f);
+  gs.p = gs.p + gq;
+  gs.n = gs.n + theta[9] * gq;
+  // t_k = start + sum_{i < k} clamp(h[i], step_min, step_max): the clamp passes the gradient on the closed interval
+  const float gt = dot_seq(gq, l);
+  gtheta[8] += gt;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) gh[i] += (i < k && h[i] >= theta[10] && h[i] <= theta[11]) ? gt : 0.0f;
+  // l = L / |L|: dL = (gl - l (gl . l)) / |L|, gl = t gq
+  const rm::V3 gl = t * gq;
+  const float gll = dot_seq(gl, l);
+  gtheta[0] += div_t<Fast>(gl.x - l.x * gll, ln);
+  gtheta[1] += div_t<Fast>(gl.y - l.y * gll, ln);
+  gtheta[2] += div_t<Fast>(gl.z - l.z * gll, ln);
+}
+template <bool Fast> RM_DEV rm::V3 marched_shadow_fwd(const rm::ShadeIn& s, const float* theta, const float* d) {
+  const rm::V3 L = mk3(theta[0], theta[1], theta[2]);
+  const float ln = norm3(L);
+  const rm::V3 l = mk3(L.x / ln, L.y / ln, L.z / ln);
+  float shadow = __builtin_inff(), t = theta[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    shadow = fminf(shadow, t_clamp((theta[7] * d[k]) / t, 0.0f, 1.0f));
+    t = t + t_clamp(d[k], theta[10], theta[11]);
+  }
+  const float c = t_clamp(dot_seq(s.n, l), 0.0f, 1.0f);
+  const float k = theta[6] + ((1.0f - theta[6]) * c) * shadow;
+  return mk3(theta[3] * k, theta[4] * k, theta[5] * k);
+}
+template <bool Fast> RM_DEV void marched_shadow_vjp(const rm::ShadeIn& s, const float* theta, const float* d, rm::V3 g, rm::ShadeGrad& gs,
+                                                    float* gtheta, float* gd) {
+  const rm::V3 L = mk3(theta[0], theta[1], theta[2]);
+  const float ln = norm3_t<Fast>(L);
+  const rm::V3 l = mk3(div_t<Fast>(L.x, ln), div_t<Fast>(L.y, ln), div_t<Fast>(L.z, ln));
+  // the first minimal step, as min(dim) reports it: its index j, the unclamped value xj, its distance dj and its ray parameter tj
+  float shadow = __builtin_inff(), xj = 0.0f, dj = 0.0f, tj = 1.0f, t = theta[8];
+  int j = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float x = div_t<Fast>(theta[7] * d[k], t);
+    const float v = t_clamp(x, 0.0f, 1.0f);
+    const bool less = v < shadow;
+    j = less ? k : j; xj = less ? x : xj; dj = less ? d[k] : dj; tj = less ? t : tj; shadow = less ? v : shadow;
+    t = t + t_clamp(d[k], theta[10], theta[11]);
+  }
+  const float dn = dot_seq(s.n, l);
+  const float c = t_clamp(dn, 0.0f, 1.0f);
+  const float lit = (1.0f - theta[6]) * c;
+  const float k = theta[6] + lit * shadow;
+  gtheta[3] = g.x * k; gtheta[4] = g.y * k; gtheta[5] = g.z * k;
+  const float gk = (g.x * theta[3] + g.y * theta[4]) + g.z * theta[5];
+  const float glit = gk * shadow, gshadow = gk * lit;
+  gtheta[6] = gk - glit * c;
+  const float gc = glit * (1.0f - theta[6]);
+  const float gdn = (dn >= 0.0f && dn <= 1.0f) ? gc : 0.0f;     // clamp passes the gradient on the closed interval
+  gs.n = gs.n + gdn * l;
+  const rm::V3 gl = gdn * s.n;
+  const float gll = dot_seq(gl, l);
+  gtheta[0] = div_t<Fast>(gl.x - l.x * gll, ln);
+  gtheta[1] = div_t<Fast>(gl.y - l.y * gll, ln);
+  gtheta[2] = div_t<Fast>(gl.z - l.z * gll, ln);
+  // shadow = clamp(xj, 0, 1), xj = sharpness dj / tj, tj = start + sum_{i < j} clamp(d_i, step_min, step_max)
+  const float gx = (xj >= 0.0f && xj <= 1.0f) ? gshadow : 0.0f;
+  const float gxt = div_t<Fast>(gx, tj);
+  gtheta[7] = gxt * dj;
+  const float gtj = -(gxt * xj);
+  gtheta[8] = gtj;
+  gtheta[9] = 0.0f; gtheta[10] = 0.0f; gtheta[11] = 0.0f;         // bias, step_min, step_max: constants (frozen), no gradient
+  const float gdj = gxt * theta[7];
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    gd[k] = ((k == j) ? gdj : 0.0f) + ((k < j && d[k] >= theta[10] && d[k] <= theta[11]) ? gtj : 0.0f);
+}
+"""
+
+register_shader(MarchedShadowShader, params=("light_direction", "albedo", "ambient", "sharpness", "start", "bias", "step_min", "step_max"),
+                hip=_MARCHED_SHADOW_HIP, probes=8, chained=True)

@@ -959,6 +959,16 @@ struct ShadeGrad {
 // alone, so both passes are flat loops over k; they stay rolled (one inlined copy of the scene evaluator each, like the taps'),
 // and d[] / gd[] are only ever indexed by constants (user_probe_push / user_probe_pop), so they stay registers.  Without
 // RM_USER_SHADER_PROBES nothing of it exists either.
+// A shader with CHAINED probes (register_shader(probes=K, chained=True), 2 <= K <= 8) also adds
+//     #define RM_USER_SHADER_PROBES_CHAINED 1,
+// and its probe pair takes the history of the chain behind theta:
+//     template <bool Fast> RM_DEV rm::V3 NAME_probe(int k, const rm::ShadeIn& s, const float* theta, const float* h);
+//     template <bool Fast> RM_DEV void   NAME_probe_vjp(int k, const rm::ShadeIn& s, const float* theta, const float* h, rm::V3 gq,
+//                                                       rm::ShadeGrad& gs, float* gtheta, float* gh);
+// h[i] (K-1 entries) is the scene's value at probe k-1-i for i < k and 0 for i >= k; the VJP adds dL/d(that value) into gh[i].
+// The forward is one rolled loop that evaluates the probes in order; the backward recomputes all K values, runs NAME_vjp, and
+// sweeps the probes last to first with two windows (h over d, g over gd) that slide by one place per probe through constant
+// indices: no checkpoint buffer, no run-time index.  Without the define the flat code above is what compiles.
 #ifdef RM_STATIC_CODE
 #define RM_STATIC_CODE_LEAVES
 #define RM_STATIC_CODE_SHADER
@@ -989,11 +999,39 @@ RM_DEV float user_probe_pop(float (&gd)[RM_USER_SHADER_PROBES]) {
 }
 // the scene at the K probe points of one pixel: the full evaluator, as for the taps (the carried cull decisions of eval_near
 // hold along the march only)
+#ifndef RM_USER_SHADER_PROBES_CHAINED
 template <class SceneT>
 RM_DEV void user_probe_values(const SceneT& scene, const ShadeIn& si, const float* theta, float (&d)[RM_USER_SHADER_PROBES]) {
 #pragma unroll RM_USER_PROBE_UNROLL
   for (int k = 0; k < RM_USER_SHADER_PROBES; ++k) user_probe_push(d, scene.eval(user_shader_probe<false>(k, si, theta)));
 }
+#else
+static_assert(RM_USER_SHADER_PROBES >= 2, "chained probes: a chain has at least two probes");
+// Chained probes: probe k is placed from the values before it, handed over as the history h[i] = d_{k-1-i} (i < k), 0 behind.
+// While d is being filled by pushes, the k values it holds sit at its END (d[K-1] the most recent) in front of the zeros it
+// started with, so the history is d read backwards through constant indices: a view, no second set of registers.
+RM_DEV void user_probe_history(const float (&d)[RM_USER_SHADER_PROBES], float (&h)[RM_USER_SHADER_PROBES - 1]) {
+#pragma unroll
+  for (int i = 0; i + 1 < RM_USER_SHADER_PROBES; ++i) h[i] = d[RM_USER_SHADER_PROBES - 1 - i];
+}
+// one place on in the reverse sweep: the window moves towards the start of the chain, zeros come in behind
+template <int N> RM_DEV void user_probe_slide(float (&w)[N]) {
+#pragma unroll
+  for (int j = 0; j + 1 < N; ++j) w[j] = w[j + 1];
+  w[N - 1] = 0.0f;
+}
+template <class SceneT>
+RM_DEV void user_probe_values(const SceneT& scene, const ShadeIn& si, const float* theta, float (&d)[RM_USER_SHADER_PROBES]) {
+#pragma unroll
+  for (int j = 0; j < RM_USER_SHADER_PROBES; ++j) d[j] = 0.0f;
+#pragma unroll RM_USER_PROBE_UNROLL
+  for (int k = 0; k < RM_USER_SHADER_PROBES; ++k) {
+    float h[RM_USER_SHADER_PROBES - 1];
+    user_probe_history(d, h);
+    user_probe_push(d, scene.eval(user_shader_probe<false>(k, si, theta, h)));
+  }
+}
+#endif
 #endif
 
 // The user shader as the forward of the frame kernels calls it: theta out of the staged block and, for a shader with probes, the
@@ -2188,12 +2226,31 @@ __global__ void __launch_bounds__(256) RM_BWD_OCC k_render_bwd(RenderArgs a) {
       float d[RM_USER_SHADER_PROBES] = {}, gd[RM_USER_SHADER_PROBES] = {};
       user_probe_values(scene, si, theta, d);
       user_shader_vjp<(RM_FAST_VJP != 0)>(si, theta, d, gi3, gs, gtheta, gd);
+#ifdef RM_USER_SHADER_PROBES_CHAINED
+      // chained probes: the reverse sweep, last probe first.  Two windows, set up from d and gd by constant indices, slide by one
+      // place per probe: h[i] = d_{k-1-i} is the history probe k was placed from, g[i] = dL/dd_{k-i}, so g[0] is the upstream of
+      // this probe's scene VJP -- complete, since every later probe has already added its share -- and g + 1 is where the probe's
+      // own VJP adds dL/d(earlier values).  (Entries behind the start of the chain: h reads 0, what lands in g is never used.)
+      float h[RM_USER_SHADER_PROBES - 1], g[RM_USER_SHADER_PROBES];
+#pragma unroll
+      for (int i = 0; i + 1 < RM_USER_SHADER_PROBES; ++i) h[i] = d[RM_USER_SHADER_PROBES - 2 - i];
+#pragma unroll
+      for (int i = 0; i < RM_USER_SHADER_PROBES; ++i) g[i] = gd[RM_USER_SHADER_PROBES - 1 - i];
+#pragma unroll RM_USER_PROBE_UNROLL
+      for (int k = RM_USER_SHADER_PROBES - 1; k >= 0; --k) {
+        const V3 gq = scene.vjp(user_shader_probe<false>(k, si, theta, h), live ? g[0] : 0.0f);
+        user_shader_probe_vjp<(RM_FAST_VJP != 0)>(k, si, theta, h, gq, gs, gtheta, &g[1]);
+        user_probe_slide(g);
+        user_probe_slide(h);
+      }
+#else
 #pragma unroll RM_USER_PROBE_UNROLL
       for (int k = 0; k < RM_USER_SHADER_PROBES; ++k) {
         const float gk = user_probe_pop(gd);
         const V3 gq = scene.vjp(user_shader_probe<false>(k, si, theta), live ? gk : 0.0f);
         user_shader_probe_vjp<(RM_FAST_VJP != 0)>(k, si, theta, gq, gs, gtheta);
       }
+#endif
 #else
       user_shader_vjp<(RM_FAST_VJP != 0)>(si, theta, gi3, gs, gtheta);
 #endif

@@ -95,13 +95,31 @@ and its own pair takes the probe values,
 
 ``NAME_probe`` returns probe ``k``, a point in world space that is a function of the pixel's ``ShadeIn`` and of ``theta`` ONLY: probes
 are independent, none may depend on the value of another (a marched shadow ray, whose next point depends on the last distance,
-is out of scope; fixed-step shadows and fixed-height occlusion are not).  The kernels evaluate ``d[k] = scene(NAME_probe(k, ..))``
+needs ``chained=True``, below; fixed-step shadows and fixed-height occlusion do not).  The kernels evaluate ``d[k] = scene(NAME_probe(k, ..))``
 with the full evaluator the normal's taps use and hand ``d`` to ``NAME_fwd``; ``NAME_vjp`` writes ``gtheta[i]`` and ``gd[k] = dL/dd[k]``,
 the kernels turn each ``gd[k]`` into the scene-parameter gradients and ``gq = dL/d(probe k)``, and ``NAME_probe_vjp`` ADDS ``J^T gq``
 into ``gs`` and ``gtheta``.  ``k`` is a run-time value in both (the probe loop stays rolled: one inlined copy of the scene): compute
 with it or select on it, never index an array with it, and index ``d`` / ``gd`` / ``theta`` / ``gtheta`` with constants only (an array
 indexed at run time goes to scratch memory).  The class's PyTorch ``forward`` takes one more trailing argument, ``scene``, a
 callable ``points[..., 3] -> [..., 1]``; with ``probes=0`` (the default) everything is as described above.
+
+*Chained probes* lift the independence: ``register_shader(..., probes=K, chained=True)`` with ``2 <= K <= RM_USER_SHADER_MAX_PROBES``
+lets probe ``k`` depend on the values the scene returned at the probes before it (a sphere-traced shadow ray, a thickness march
+along ``-n``, a short reflection march, adaptive-height occlusion).  The probe pair then takes a *history*,
+
+    template <bool Fast> RM_DEV rm::V3 NAME_probe    (int k, const rm::ShadeIn& s, const float* theta, const float* h);
+    template <bool Fast> RM_DEV void   NAME_probe_vjp(int k, const rm::ShadeIn& s, const float* theta, const float* h, rm::V3 gq,
+                                                      rm::ShadeGrad& gs, float* gtheta, float* gh);
+
+``h`` and ``gh`` have K-1 entries and are RELATIVE to ``k``: ``h[i]`` is the scene's value at probe ``k-1-i`` for ``i < k`` (``h[0]`` the
+most recent one, ``h[1]`` the one before) and exactly ``0.0f`` for ``i >= k``, so that a marched ray's ``t_k = t_0 + sum_i f(h[i])`` needs no
+masking where the author sees to ``f(0) = 0``.  ``NAME_probe_vjp`` ADDS ``dL/d(value of probe k-1-i)`` into ``gh[i]``; whatever it adds to
+``gh[i]`` with ``i >= k`` is ignored.  ``NAME_fwd`` / ``NAME_vjp`` keep the probing signature (``d[0..K-1]`` in probe order, ``gd`` out): the
+kernels evaluate the probes in order, run ``NAME_vjp``, then walk the probes last to first and hand each one's ``gh`` back to the
+earlier values before their own scene VJP runs (K <= 8: the whole chain is in registers, nothing is checkpointed).  ``h``, ``gh``,
+``d`` and ``gd`` must only be indexed by constants, like ``d`` / ``gd`` above: ``k`` is a run-time value, and the window slides by one place
+per probe through constant indices precisely so that no array is ever indexed with it.  The class's PyTorch ``forward(..., scene)``
+needs nothing new: it calls ``scene`` in sequence and autograd does the rest.
 
 Scenes that contain such a leaf, combinator or warp, and frames shaded by such a shader, run only through their per-scene specialised library (specialize.py), into which
 the source is compiled; the LDS interpreter has no handler for them and ``CompiledScene.lib()`` says so instead of
@@ -161,6 +179,7 @@ class UserShader(_UserSpec):
     kind = "shader"
     sha1: str
     probes: int = 0     # K: the scene evaluations the shader asks for per pixel (NAME_probe / NAME_probe_vjp); 0: none
+    chained: bool = False   # probe k may depend on the values of the probes before it (the pair takes the history h / gh)
 
 
 @dataclass(frozen=True)
@@ -206,7 +225,7 @@ _KINDS = {
         "`template <bool Fast> RM_DEV void NAME_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 g, rm::ShadeGrad& gs, float* "
         "gtheta)`",
         methods=(("forward", "forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals)"),),
-        same=("sha1", "params", "probes"), device_forward=False, probe_pair=True),
+        same=("sha1", "params", "probes", "chained"), device_forward=False, probe_pair=True),
 }
 
 RM_USER_SHADER_MAX_PROBES = 8       # the most scene probes a shader may ask for (d[] / gd[] live in registers: INTEGRATION.md)
@@ -331,6 +350,12 @@ def _register(kind: str, cls, *, params, hip: str, **own):
             raise ValueError(f"{fn}: the source of {cls.__name__} defines {name}_probe / {name}_probe_vjp, but probes=0")
         if probes > 0 and not has_probe:
             raise ValueError(f"{fn}: probes={probes}, but the source of {cls.__name__} defines no {name}_probe / {name}_probe_vjp")
+        chained = own["chained"]
+        if not isinstance(chained, bool):
+            raise ValueError(f"{fn}: chained must be a bool, not {chained!r}")
+        if chained and probes < 2:
+            raise ValueError(f"{fn}: chained=True needs probes from 2 to RM_USER_SHADER_MAX_PROBES = {RM_USER_SHADER_MAX_PROBES} (a chain of "
+                             f"one probe has no history), not probes={probes}")
     if row.out_pair and has_out != callable(getattr(cls, "out", None)):
         raise TypeError(f"{fn}: {cls.__name__} " + (
             f"has no out(values, points) method, but its source defines {name}_out_fwd / {name}_out_vjp" if has_out else
@@ -348,7 +373,8 @@ def _register(kind: str, cls, *, params, hip: str, **own):
     if old is not None:
         if any(getattr(old, f) != getattr(spec, f) for f in row.same):
             raise ValueError(f"{fn}: {cls.__name__} is already registered with different {row.different}"
-                             + (" (or another number of probes)" if row.probe_pair and old.probes != spec.probes else ""))
+                             + (" (or another number of probes)" if row.probe_pair and old.probes != spec.probes else "")
+                             + (f" (chained={old.chained} before, chained={spec.chained} now)" if row.probe_pair and old.chained != spec.chained else ""))
         return cls
     for other in _registry.values():
         if other.name == spec.name:          # (a scene's user types and the shader are compiled into one translation unit)
@@ -444,7 +470,7 @@ def warp_child(node, spec: UserWarp):
     return kid
 
 
-def register_shader(cls, *, params=(), hip: str, probes: int = 0):
+def register_shader(cls, *, params=(), hip: str, probes: int = 0, chained: bool = False):
     """Make instances of ``cls`` (an ``nn.Module`` subclass) usable as the ``mode`` of ``RenderLoop.forward``: a per-pixel shader
     that runs fused at the end of the frame kernels and in the fused backward.
 
@@ -454,12 +480,16 @@ def register_shader(cls, *, params=(), hip: str, probes: int = 0):
             RM_USER_SHADER_MAX_PROBES = 8.  With K > 0 the source brings NAME_probe / NAME_probe_vjp, NAME_fwd / NAME_vjp take the
             probe values ``d`` (and ``gd``), and ``forward`` takes a trailing ``scene`` argument, a callable ``points[..., 3] ->
             [..., 1]`` (module docstring: "scene probes").
+    chained: probe ``k`` may depend on the values of the probes before it (needs ``2 <= K``): NAME_probe / NAME_probe_vjp take the
+            history ``const float* h`` behind theta (the VJP also ``float* gh`` at its end), K-1 entries relative to ``k``, ``h[0]`` the
+            most recent value, zeros where there is none yet; index ``h`` / ``gh`` / ``d`` / ``gd`` with constants only (module docstring:
+            "chained probes").
 
     ``cls`` has ``forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals) -> [..., 3]``,
     the first six arguments of the reference's ``Shader.forward`` (``camera_orientation`` [N,4], ``pixel_frames`` [N,3,3]); it is
     the CPU statement of the shader and is NOT replaced.  Registering a class again with the same source is a no-op; with other
-    source, parameters or number of probes it is an error.  Identifiers are unique across all four kinds (leaves, combinators, warps and shaders)."""
-    return _register("shader", cls, params=params, hip=hip, probes=probes)
+    source, parameters, number of probes or value of ``chained`` it is an error.  Identifiers are unique across all four kinds (leaves, combinators, warps and shaders)."""
+    return _register("shader", cls, params=params, hip=hip, probes=probes, chained=chained)
 
 
 def shader_spec(node):

@@ -173,7 +173,8 @@ def _warp_section(cs: CompiledScene) -> str:
 def _shader_section(cs: CompiledScene) -> str:
     """The user shader's source and the functions the frame kernels call, for the header's inclusion from csrc/rm_kernels.h
     (behind rm::ShadeIn / rm::ShadeGrad, inside namespace rm): two, or -- a shader with scene probes, RM_USER_SHADER_PROBES --
-    four, of which user_shader_fwd / user_shader_vjp then carry the probe values."""
+    four, of which user_shader_fwd / user_shader_vjp then carry the probe values; the probe pair of a chained shader
+    (RM_USER_SHADER_PROBES_CHAINED) also carries the history ``h`` of the values before probe ``k`` and, in the VJP, ``gh``."""
     name, floats, sha = cs.user_shader
     k = cs.user_shader_probes
     head = ("#define RM_USER_SHADER 1\n"
@@ -187,14 +188,25 @@ def _shader_section(cs: CompiledScene) -> str:
             f"  return {name}_fwd<Fast>(s, theta);\n}}\n"
             "template <bool Fast> RM_DEV void user_shader_vjp(const ShadeIn& s, const float* theta, V3 g, ShadeGrad& gs, float* gtheta) {\n"
             f"  {name}_vjp<Fast>(s, theta, g, gs, gtheta);\n}}\n")
+    if cs.user_shader_chained:
+        probe_pair = (
+            "#define RM_USER_SHADER_PROBES_CHAINED 1\n"
+            + f"// user shader: {name}, {floats} parameter floats, {k} chained scene probes, sha1 {sha}\n{cs.user_shader_source.strip()}\n"
+            "template <bool Fast> RM_DEV V3 user_shader_probe(int k, const ShadeIn& s, const float* theta, const float* h) {\n"
+            f"  return {name}_probe<Fast>(k, s, theta, h);\n}}\n"
+            "template <bool Fast> RM_DEV void user_shader_probe_vjp(int k, const ShadeIn& s, const float* theta, const float* h, V3 gq, "
+            "ShadeGrad& gs, float* gtheta, float* gh) {\n"
+            f"  {name}_probe_vjp<Fast>(k, s, theta, h, gq, gs, gtheta, gh);\n}}\n")
+    else:
+        probe_pair = (
+            f"// user shader: {name}, {floats} parameter floats, {k} scene probes, sha1 {sha}\n{cs.user_shader_source.strip()}\n"
+            "template <bool Fast> RM_DEV V3 user_shader_probe(int k, const ShadeIn& s, const float* theta) {\n"
+            f"  return {name}_probe<Fast>(k, s, theta);\n}}\n"
+            "template <bool Fast> RM_DEV void user_shader_probe_vjp(int k, const ShadeIn& s, const float* theta, V3 gq, ShadeGrad& gs, "
+            "float* gtheta) {\n"
+            f"  {name}_probe_vjp<Fast>(k, s, theta, gq, gs, gtheta);\n}}\n")
     return (
-        head + f"#define RM_USER_SHADER_PROBES {k}\n"
-        + f"// user shader: {name}, {floats} parameter floats, {k} scene probes, sha1 {sha}\n{cs.user_shader_source.strip()}\n"
-        "template <bool Fast> RM_DEV V3 user_shader_probe(int k, const ShadeIn& s, const float* theta) {\n"
-        f"  return {name}_probe<Fast>(k, s, theta);\n}}\n"
-        "template <bool Fast> RM_DEV void user_shader_probe_vjp(int k, const ShadeIn& s, const float* theta, V3 gq, ShadeGrad& gs, "
-        "float* gtheta) {\n"
-        f"  {name}_probe_vjp<Fast>(k, s, theta, gq, gs, gtheta);\n}}\n"
+        head + f"#define RM_USER_SHADER_PROBES {k}\n" + probe_pair +
         "template <bool Fast> RM_DEV V3 user_shader_fwd(const ShadeIn& s, const float* theta, const float* d) {\n"
         f"  return {name}_fwd<Fast>(s, theta, d);\n}}\n"
         "template <bool Fast> RM_DEV void user_shader_vjp(const ShadeIn& s, const float* theta, const float* d, V3 g, ShadeGrad& gs, "
