@@ -187,7 +187,8 @@ enum {
                               parameter block.  Accepted by rm_render_forward / rm_render_backward of a library that reports
                               rm_user_shaders() == 1 and refused by every other; rm_shade_forward / rm_shade_backward, which have no
                               scene and hence no theta, never take it.  Per pixel, [.., 3] like the other ungrouped modes (no global
-                              normalisation, no colormap); the frame evaluates neither the Laplacian nor scene(p) for it */
+                              normalisation, no colormap -- unless the shader was registered with normalise="minmax":
+                              rm_user_shade_finish below); the frame evaluates neither the Laplacian nor scene(p) for it */
 };
 
 /* flags */
@@ -434,6 +435,25 @@ int rm_render_backward(const RmScene* scene, const RmCamera* cam, const RmTetra*
 #define RM_NORM_BWD_BLOCKS 1024
 int rm_shade_norm_backward(const float* raw, const float* grad_image, const float* lohi /*device [2]*/, int32_t mode,
                            float* grad_raw, float* partials, int64_t n_pixels, void* stream);
+
+/* A user shader normalised by the frame's min / max (extensions.register_shader(normalise="minmax")): the library of such a
+ * (scene, shader) pair compiles NAME_finish / NAME_finish_vjp in, its rm_render_forward treats RM_MODE_USER like modes 1 and 2 (the
+ * raw triple NAME_fwd returns goes to `first_pass`, which is then required like `minmax`, and raw.x of every live pixel into the
+ * min / max / NaN words), and the two entry points below are its second pass and that pass's VJP.  Every other library -- the
+ * generic ones, scenes alone, per-pixel user shaders -- answers both with RM_E_BADARG, as it answers RM_MODE_USER.
+ * `scene`: the RmScene of the frame; only the shader's parameter floats are read (from `block`, `param_refs` or `params`, in that
+ * order), nothing is staged or derived.
+ * rm_user_shade_finish: first_pass fp32 [n_pixels,3] -> image [n_pixels,3] of image_dtype (F32, F16, or RGBA_F32 [n_pixels,4] with
+ * round_dtype as in rm_shade_finish); in place when the two pointers are equal (F32 only).
+ * rm_user_shade_norm_backward: raw = first_pass, lohi = device {min, max} (rm_minmax_decode), grad_image = dL/d(image) [n,3];
+ * grad_raw [n,3] out = dL/d(raw) with the frame's dL/dlo and dL/dhi shared evenly among the pixels whose raw.x attains them: the
+ * `grad_image` rm_render_backward expects for such a library; grad_theta [P] out = the second pass's own dL/dtheta, to be ADDED to
+ * the shader's slice of rm_render_backward's grad_params.  partials: RM_NORM_BWD_BLOCKS * (4 + P) floats, P = the shader's
+ * parameter floats.  Two launches; deterministic (fixed summation order). */
+int rm_user_shade_finish(const RmScene* scene, const float* first_pass, void* image, int32_t image_dtype, int64_t n_pixels,
+                         const uint32_t* minmax, int32_t round_dtype, void* stream);
+int rm_user_shade_norm_backward(const RmScene* scene, const float* raw, const float* grad_image, const float* lohi /*device [2]*/,
+                                float* grad_raw, float* grad_theta, float* partials, int64_t n_pixels, void* stream);
 
 /* out[width] = sum over n_rows rows of rows[n_rows][width], fixed summation tree (deterministic). */
 int rm_sum_rows(const float* rows, int64_t n_rows, int32_t width, float* out, void* stream);

@@ -109,6 +109,8 @@ _SIGNATURES = {
                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
     "rm_sum_rows": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P]),
     "rm_shade_norm_backward": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int64, _P]),
+    "rm_user_shade_finish": (C.c_int, [C.POINTER(RmScene), _P, _P, C.c_int32, C.c_int64, _P, C.c_int32, _P]),
+    "rm_user_shade_norm_backward": (C.c_int, [C.POINTER(RmScene), _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "rm_bwd_hard_floats": (C.c_int64, [C.c_int64, C.c_int32]),
     "rm_camera_backward": (C.c_int, [C.POINTER(RmCamera), _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
 }

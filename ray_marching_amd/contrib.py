@@ -928,3 +928,73 @@ template <bool Fast> RM_DEV void marched_shadow_vjp(const rm::ShadeIn& s, const 
 
 register_shader(MarchedShadowShader, params=("light_direction", "albedo", "ambient", "sharpness", "start", "bias", "step_min", "step_max"),
                 hip=_MARCHED_SHADOW_HIP, probes=8, chained=True)
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# Shaders normalised by the frame's min / max (register_shader(normalise="minmax")): a first pass per pixel, the frame's extremes,
+# a second pass -- what the reference's distance, proximity and Laplacian modes do, open to users
+# --------------------------------------------------------------------------------------------------------------------
+class DepthRampShader(nn.Module):
+    """A depth ramp that adapts to the scene's extent: ``x = clamp(|o - p|, clip_near, clip_far)``, ``t = (x - min x) / (max x - min x)``
+    over every pixel of every camera of the frame, ``rgb = near_colour + t * (far_colour - near_colour)``.  The two colours are
+    trainable (six floats); ``clip_near`` and ``clip_far`` are constructor constants kept as frozen ``nn.Parameter``s, so that they
+    travel in theta.  No power and no logarithm: its gradients are finite everywhere (the built-in distance mode's ``pow(1 / 2.33)``
+    has an infinite slope at the frame's minimum), and a pixel the clamp cuts off passes none.  A frame in which every pixel has
+    the same depth (``min == max``) is 0 / 0."""
+
+    def __init__(self, near_colour=(1.0, 0.9, 0.7), far_colour=(0.05, 0.1, 0.3), clip_near: float = 0.0,
+                 clip_far: float = float("inf")) -> None:
+        super().__init__()
+        self.near_colour = nn.Parameter(torch.tensor(near_colour, dtype=torch.float32))
+        self.far_colour = nn.Parameter(torch.tensor(far_colour, dtype=torch.float32))
+        self.clip_near = nn.Parameter(torch.tensor(clip_near, dtype=torch.float32), requires_grad=False)
+        self.clip_far = nn.Parameter(torch.tensor(clip_far, dtype=torch.float32), requires_grad=False)
+
+    def forward(self, px_coords: Tensor, camera_orientation: Tensor, pixel_frames: Tensor, ray_directions: Tensor,
+                surface_coords: Tensor, surface_normals: Tensor) -> Tensor:
+        x = torch.linalg.vector_norm(px_coords - surface_coords, dim=-1, keepdim=True).clamp(self.clip_near, self.clip_far)
+        lo, hi = x.min(), x.max()
+        t = (x - lo) / (hi - lo)
+        return self.near_colour + t * (self.far_colour - self.near_colour)
+
+
+# theta = {near_colour[3], far_colour[3], clip_near, clip_far}.  depth_ramp_fwd returns the raw triple (x, 0, 0); the frame takes
+# lo = min x, hi = max x; depth_ramp_finish is the ramp.  Its VJP is autograd's, written out: t = a / r with a = x - lo, r = hi - lo,
+# so dL/dx = gt / r, dL/dr = -gt a / r^2, dL/dlo = -dL/dx - dL/dr, dL/dhi = dL/dr (this pixel's shares: the kernels sum them).
+_DEPTH_RAMP_HIP = r"""
+template <bool Fast> RM_DEV rm::V3 depth_ramp_fwd(const rm::ShadeIn& s, const float* theta) {
+  return mk3(t_clamp(norm3(s.o - s.p), theta[6], theta[7]), 0.0f, 0.0f);
+}
+template <bool Fast> RM_DEV void depth_ramp_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 g, rm::ShadeGrad& gs, float* gtheta) {
+  const rm::V3 d = s.o - s.p;
+  const float dist = norm3_t<Fast>(d);
+  const float gdist = (dist >= theta[6] && dist <= theta[7]) ? g.x : 0.0f;   // clamp passes the gradient on the closed interval
+  const float sc = (dist == 0.0f) ? 0.0f : div_t<Fast>(gdist, dist);         // norm backward: self * (grad / norm), 0 where norm == 0
+  const rm::V3 gd = sc * d;
+  gs.o = gs.o + gd;
+  gs.p = gs.p - gd;
+  gtheta[0] = 0.0f; gtheta[1] = 0.0f; gtheta[2] = 0.0f; gtheta[3] = 0.0f; gtheta[4] = 0.0f; gtheta[5] = 0.0f;   // the colours act in the second pass
+  gtheta[6] = 0.0f; gtheta[7] = 0.0f;                                        // clip_near, clip_far: constants (frozen), no gradient
+}
+template <bool Fast> RM_DEV rm::V3 depth_ramp_finish(rm::V3 raw, float lo, float hi, const float* theta) {
+  const float t = (raw.x - lo) / (hi - lo);
+  return mk3(theta[0] + t * (theta[3] - theta[0]), theta[1] + t * (theta[4] - theta[1]), theta[2] + t * (theta[5] - theta[2]));
+}
+template <bool Fast> RM_DEV void depth_ramp_finish_vjp(rm::V3 raw, float lo, float hi, const float* theta, rm::V3 g, rm::V3& graw,
+                                                       float& glo, float& ghi, float* gtheta) {
+  const float a = raw.x - lo, r = hi - lo;
+  const float t = div_t<Fast>(a, r);
+  const rm::V3 gd = mk3(g.x * t, g.y * t, g.z * t);               // dL/d(far_colour - near_colour)
+  gtheta[0] = g.x - gd.x; gtheta[1] = g.y - gd.y; gtheta[2] = g.z - gd.z;
+  gtheta[3] = gd.x; gtheta[4] = gd.y; gtheta[5] = gd.z;
+  gtheta[6] = 0.0f; gtheta[7] = 0.0f;
+  const float gt = (g.x * (theta[3] - theta[0]) + g.y * (theta[4] - theta[1])) + g.z * (theta[5] - theta[2]);
+  const float ga = div_t<Fast>(gt, r);
+  const float gr = div_t<Fast>(-gt * a, r * r);
+  graw = mk3(ga, 0.0f, 0.0f);
+  ghi = gr;
+  glo = -ga - gr;
+}
+"""
+
+register_shader(DepthRampShader, params=("near_colour", "far_colour", "clip_near", "clip_far"), hip=_DEPTH_RAMP_HIP, normalise="minmax")

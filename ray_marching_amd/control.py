@@ -416,7 +416,7 @@ class RenderLoop(nn.Module):
         """-> image [N, H, W, 3] in the module's dtype (modes 6, 7: promoted with the colormap's, float64 for
         the reference's data file).  ``rows=(r0, r1)`` renders only that pixel-row band ([N, r1-r0, W, 3]);
         ``allreduce_minmax`` is the hook row-tiled multi-GPU rendering uses for the global min/max of modes
-        1/2/5 (see ray_marching_amd/distributed.py); ``tile_order`` / ``tile_cost``: rm_render_forward's
+        1/2/5 and of user shaders registered with ``normalise="minmax"`` (see ray_marching_amd/distributed.py); ``tile_order`` / ``tile_cost``: rm_render_forward's
         scheduling hint and per-tile cost output (include/rm_abi.h).  ``mode``: one of the reference's eight shaders, or an
         instance of a class registered with extensions.register_shader ([N, H, W, 3] in the module's dtype; its own
         parameters receive gradients like the scene's)."""

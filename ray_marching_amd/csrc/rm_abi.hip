@@ -369,7 +369,8 @@ int rm_render_forward(const RmScene* scene, const RmCamera* cam, const RmTetra* 
   if (int e = check_render(scene, cam, tetra, orientation, translation, steps, row_begin, row_end)) return e;
   if (!image) return fail(RM_E_BADARG, "rm_render_forward: null image");
   if (mode < 0 || mode > kMaxMode) return fail(RM_E_BADARG, "rm_render_forward: mode %d not in 0..%d", mode, kMaxMode);
-  const bool global = (mode == RM_MODE_DISTANCE || mode == RM_MODE_PROXIMITY || mode == RM_MODE_LAPLACIAN);
+  const bool global = (mode == RM_MODE_DISTANCE || mode == RM_MODE_PROXIMITY || mode == RM_MODE_LAPLACIAN) ||
+                      (rm::UserShader::kNormalise && mode == RM_MODE_USER);      // (a user shader normalised by the frame's min / max)
   const bool mapped = (mode == RM_MODE_TANGENT || mode == RM_MODE_SPIN);
   if (global && (!minmax || !first_pass))
     return fail(RM_E_BADARG, "rm_render_forward: mode %d needs a minmax workspace and a first_pass buffer", mode);
@@ -568,6 +569,44 @@ int rm_shade_norm_backward(const float* raw, const float* grad_image, const floa
   rm::k_shade_norm_bwd_b<<<grid_for((n_pixels + 255) / 256, kMaxBlocks), 256, 0, (hipStream_t)stream>>>(raw, lohi, mode, grad_raw, partials,
                                                                                                      blocks, n_pixels);
   return launched("k_shade_norm_bwd_b");
+}
+
+int rm_user_shade_finish(const RmScene* scene, const float* first_pass, void* image, int32_t image_dtype, int64_t n_pixels,
+                         const uint32_t* minmax, int32_t round_dtype, void* stream) {
+#ifndef RM_USER_SHADER_NORMALISE
+  (void)scene; (void)first_pass; (void)image; (void)image_dtype; (void)n_pixels; (void)minmax; (void)round_dtype; (void)stream;
+  return fail(RM_E_BADARG, "rm_user_shade_finish: no user shader normalised by the frame's min / max was compiled into this library");
+#else
+  if (int e = check_scene(scene)) return e;
+  if (!first_pass || !image || !minmax || n_pixels < 0) return fail(RM_E_BADARG, "rm_user_shade_finish: bad args");
+  if (!(io_dtype_ok(image_dtype) || image_dtype == RM_DTYPE_RGBA_F32) || !io_dtype_ok(round_dtype) ||
+      (image_dtype != RM_DTYPE_F32 && (const void*)first_pass == (const void*)image))
+    return fail(RM_E_BADARG, "rm_user_shade_finish: image dtype %d (in place only for F32)", image_dtype);
+  if (image_dtype == RM_DTYPE_RGBA_F32 && (reinterpret_cast<uintptr_t>(image) & 15))
+    return fail(RM_E_BADARG, "rm_user_shade_finish: an RGBA_F32 image must be 16-byte aligned");
+  if (n_pixels == 0) return RM_OK;
+  int grid = grid_for((n_pixels + 255) / 256, RM_NORM_BWD_BLOCKS);
+  rm::k_user_shade_finish<<<grid, 256, 0, (hipStream_t)stream>>>(*scene, first_pass, image, image_dtype, n_pixels, minmax, round_dtype);
+  return launched("k_user_shade_finish");
+#endif
+}
+
+int rm_user_shade_norm_backward(const RmScene* scene, const float* raw, const float* grad_image, const float* lohi, float* grad_raw,
+                                float* grad_theta, float* partials, int64_t n_pixels, void* stream) {
+#ifndef RM_USER_SHADER_NORMALISE
+  (void)scene; (void)raw; (void)grad_image; (void)lohi; (void)grad_raw; (void)grad_theta; (void)partials; (void)n_pixels; (void)stream;
+  return fail(RM_E_BADARG, "rm_user_shade_norm_backward: no user shader normalised by the frame's min / max was compiled into this library");
+#else
+  if (int e = check_scene(scene)) return e;
+  if (n_pixels < 0 || (n_pixels > 0 && (!raw || !grad_image || !lohi || !grad_raw || !partials)) || (rm::kUserP > 0 && !grad_theta))
+    return fail(RM_E_BADARG, "rm_user_shade_norm_backward: null buffer");
+  if (n_pixels == 0) return RM_OK;
+  const int blocks = grid_for((n_pixels + 255) / 256, RM_NORM_BWD_BLOCKS);
+  rm::k_user_norm_bwd_a<<<blocks, 256, 0, (hipStream_t)stream>>>(*scene, raw, grad_image, lohi, grad_raw, partials, n_pixels);
+  if (int e = launched("k_user_norm_bwd_a")) return e;
+  rm::k_user_norm_bwd_b<<<blocks, 256, 0, (hipStream_t)stream>>>(raw, lohi, grad_raw, partials, blocks, grad_theta, n_pixels);
+  return launched("k_user_norm_bwd_b");
+#endif
 }
 
 int rm_camera_backward(const RmCamera* cam, const float* orientation, const float* grad_pos, const float* grad_dirs,

@@ -1055,7 +1055,22 @@ struct UserShader {
   RM_DEV V3 fwd(const ShadeIn& si) const { return user_shader_fwd<false>(si, theta.v); }
 #endif
 #endif
+  // A shader normalised by the frame's min / max (register_shader(normalise="minmax"): RM_USER_SHADER_NORMALISE, with
+  // user_shader_finish / user_shader_finish_vjp in the header): what fwd returns is the pixel's raw triple, which the frame
+  // kernels leave in first_pass and whose .x they fold into the min / max words, like the distance and proximity modes'.
+#ifdef RM_USER_SHADER_NORMALISE
+  static constexpr bool kNormalise = true;
+#else
+  static constexpr bool kNormalise = false;
+#endif
 };
+// ... so RM_MODE_USER joins the tests that single those modes out -- as text: in every other library the tests are, token for
+// token, what they were, and so is the code they compile to
+#ifdef RM_USER_SHADER_NORMALISE
+#define RM_OR_USER_NORMALISED(mode) || (mode) == RM_MODE_USER
+#else
+#define RM_OR_USER_NORMALISED(mode)
+#endif
 
 // third column of the camera rotation (QuaternionToSO3, quaternion.py:114-124): pixel_frames[..., 2]
 RM_DEV V3 col2_of(const Pose& ps) {
@@ -1369,15 +1384,15 @@ RM_DEV void finish_tile(const RenderArgs& a, const SceneT& scene, const Tetra& T
   if (UserShader::kEnabled && mode == RM_MODE_USER) us.probe(scene, si);   // (mode is uniform: every lane of the wave evaluates)
   const Shaded sh = shade_pixel(mode, si, a.cmap_size, a.degree, &us);
   const V3 out = sh.rgb;
-  const bool global = (mode == RM_MODE_DISTANCE || mode == RM_MODE_PROXIMITY || mode == RM_MODE_LAPLACIAN);
+  const bool global = (mode == RM_MODE_DISTANCE || mode == RM_MODE_PROXIMITY || mode == RM_MODE_LAPLACIAN RM_OR_USER_NORMALISED(mode));
   if (r.live) {
-    if (global) store3(a.first_pass, r.li, out);          // rm_shade_finish normalises into `image`
+    if (global) store3(a.first_pass, r.li, out);          // rm_shade_finish (rm_user_shade_finish) normalises into `image`
     else store_shaded(a.image, a.image_dtype, r.li, sh, a.cmap, a.cmap_dtype, a.cam.dtype);
     if constexpr (kAux) {
       if (store_p && a.p_final) store3(a.p_final, r.li, p);
       if (a.nexec) a.nexec[r.li] = nexec;
     }
-    if (mode == RM_MODE_DISTANCE || mode == RM_MODE_PROXIMITY) {
+    if (mode == RM_MODE_DISTANCE || mode == RM_MODE_PROXIMITY RM_OR_USER_NORMALISED(mode)) {
       mm.saw_nan |= (out.x != out.x);
       mm.lo = fminf(mm.lo, out.x); mm.hi = fmaxf(mm.hi, out.x);
     } else if (mode == RM_MODE_LAPLACIAN) {
@@ -1445,7 +1460,7 @@ __global__ void __launch_bounds__(256) k_render_fwd(RenderArgs a) {
     r.live = r.live && !parked;                 // a parked ray's pixel is written by k_render_parked
     finish_tile<decltype(scene), kRecord>(a, scene, T, r, p, nexec, mm);
   }
-  if (a.minmax && (a.mode == RM_MODE_DISTANCE || a.mode == RM_MODE_PROXIMITY || a.mode == RM_MODE_LAPLACIAN))
+  if (a.minmax && (a.mode == RM_MODE_DISTANCE || a.mode == RM_MODE_PROXIMITY || a.mode == RM_MODE_LAPLACIAN RM_OR_USER_NORMALISED(a.mode)))
     fold_minmax(a.minmax, mm.lo, mm.hi, mm.saw_nan);
 }
 
@@ -1490,7 +1505,7 @@ __global__ void __launch_bounds__(256) k_render_parked(RenderArgs a) {
     }
     before += n_items;
   }
-  if (a.minmax && (a.mode == RM_MODE_DISTANCE || a.mode == RM_MODE_PROXIMITY || a.mode == RM_MODE_LAPLACIAN))
+  if (a.minmax && (a.mode == RM_MODE_DISTANCE || a.mode == RM_MODE_PROXIMITY || a.mode == RM_MODE_LAPLACIAN RM_OR_USER_NORMALISED(a.mode)))
     fold_minmax(a.minmax, mm.lo, mm.hi, mm.saw_nan);
 }
 
@@ -1715,7 +1730,7 @@ __global__ void __launch_bounds__(256) k_render_finish(RenderArgs a) {
     const V3 p = load3(a.p_final, r.li);
     finish_tile(a, scene, T, r, p, a.steps, mm, false);
   }
-  if (a.minmax && (a.mode == RM_MODE_DISTANCE || a.mode == RM_MODE_PROXIMITY || a.mode == RM_MODE_LAPLACIAN))
+  if (a.minmax && (a.mode == RM_MODE_DISTANCE || a.mode == RM_MODE_PROXIMITY || a.mode == RM_MODE_LAPLACIAN RM_OR_USER_NORMALISED(a.mode)))
     fold_minmax(a.minmax, mm.lo, mm.hi, mm.saw_nan);
 }
 
@@ -1981,6 +1996,97 @@ __global__ void __launch_bounds__(256) k_shade_norm_bwd_b(const float* __restric
     out[3 * i] = v; out[3 * i + 1] = 0.0f; out[3 * i + 2] = 0.0f;
   }
 }
+
+#ifdef RM_USER_SHADER_NORMALISE
+// ---- second pass of a user shader normalised by the frame's min / max, and its VJP ------------------------------------------
+// (register_shader(normalise="minmax"); libraries whose header defines RM_USER_SHADER_NORMALISE only.)  The frame kernels left
+// NAME_fwd's raw triple in first_pass and folded raw.x into the min / max words; user_shader_finish(raw, lo, hi, theta) makes the
+// pixel.  The three kernels stage no scene block and derive nothing: all they need of the scene are the shader's
+// RM_USER_SHADER_PARAMS floats, read where the frame kernel finds its parameters (the finished block of an earlier launch, the
+// pointer table, or the packed block), so in-place edits and optimiser steps are simply what they read.  P is a constant of the
+// library: theta, gtheta and the partial row are indexed by constants only and stay registers.
+constexpr int kUserP = RM_USER_SHADER_PARAMS;
+constexpr int kUserPn = kUserP > 0 ? kUserP : 1;
+constexpr int kUserNormRow = 4 + kUserP;        // one row of partials: sum glo, sum ghi, #[raw.x == lo], #[raw.x == hi], gtheta[P]
+
+RM_DEV void user_theta_load(const RmScene& sc, float (&theta)[kUserPn]) {
+#pragma unroll
+  for (int i = 0; i < kUserP; ++i) {
+    const int at = RM_USER_SHADER_THETA + i;
+    if (sc.block) theta[i] = sc.block[at];
+    else if (sc.param_refs) { const RmParamRef r = sc.param_refs[at]; theta[i] = ld_t(r.base, r.elem, r.dtype); }
+    else theta[i] = sc.params[at];
+  }
+}
+
+// grid-stride; `image` may be `src` itself when it is fp32 (a pixel is read and written by one thread)
+__global__ void __launch_bounds__(256) k_user_shade_finish(RmScene sc, const float* src, void* image, int dt, int64_t n,
+                                                           const uint32_t* __restrict__ minmax, int round_dt) {
+  float lo, hi;
+  load_minmax(minmax, lo, hi);
+  float theta[kUserPn] = {};
+  user_theta_load(sc, theta);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const V3 y = user_shader_finish<false>(load3(src, i), lo, hi, theta);
+    if (dt == RM_DTYPE_RGBA_F32) store_rgba(image, i, y, round_dt);
+    else store3_t(image, i, y, dt);          // the one rounding of a float16 image
+  }
+}
+
+// Pass A: NAME_finish_vjp per pixel; graw (all three channels) to `out`, the frame sums per block, each by the fixed tree of
+// block_sum_256, into partials[block][kUserNormRow].  Selects, not products: a NaN pixel counts for neither end.
+__global__ void __launch_bounds__(256) k_user_norm_bwd_a(RmScene sc, const float* __restrict__ raw, const float* __restrict__ grad_image,
+                                                         const float* __restrict__ lohi, float* __restrict__ out,
+                                                         float* __restrict__ partials, int64_t n) {
+  __shared__ float red[256];
+  const float lo = lohi[0], hi = lohi[1];
+  float theta[kUserPn] = {};
+  user_theta_load(sc, theta);
+  float row[kUserNormRow] = {};
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const V3 x = load3(raw, i);
+    V3 graw = mk3(0.0f, 0.0f, 0.0f);
+    float glo = 0.0f, ghi = 0.0f, gtheta[kUserPn] = {};
+    user_shader_finish_vjp<(RM_FAST_VJP != 0)>(x, lo, hi, theta, load3(grad_image, i), graw, glo, ghi, gtheta);
+    store3(out, i, graw);
+    row[0] += glo; row[1] += ghi;
+    row[2] += (x.x == lo) ? 1.0f : 0.0f; row[3] += (x.x == hi) ? 1.0f : 0.0f;      // exact below 2^24 pixels per thread
+#pragma unroll
+    for (int k = 0; k < kUserP; ++k) row[4 + k] += gtheta[k];
+  }
+#pragma unroll
+  for (int k = 0; k < kUserNormRow; ++k) {
+    const float s = block_sum_256(row[k], red);
+    if (threadIdx.x == 0) partials[(int64_t)kUserNormRow * blockIdx.x + k] = s;
+  }
+}
+
+// Pass B: every block adds the rows of pass A up in ONE fixed order (thread t rows t, t + 256, ..., then the tree), so the
+// sums are the same bits in every block and in every run; then the two end terms, shared evenly among the pixels that attain
+// the extremum (torch.min() / torch.max()), join graw.x.  Block 0 writes the P sums of gtheta.
+__global__ void __launch_bounds__(256) k_user_norm_bwd_b(const float* __restrict__ raw, const float* __restrict__ lohi,
+                                                         float* __restrict__ out, const float* __restrict__ partials, int n_partials,
+                                                         float* __restrict__ grad_theta, int64_t n) {
+  __shared__ float red[256];
+  float row[kUserNormRow] = {};
+  for (int b = threadIdx.x; b < n_partials; b += 256) {
+#pragma unroll
+    for (int k = 0; k < kUserNormRow; ++k) row[k] += partials[(int64_t)kUserNormRow * b + k];
+  }
+#pragma unroll
+  for (int k = 0; k < kUserNormRow; ++k) row[k] = block_sum_256(row[k], red);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < kUserP; ++k) grad_theta[k] = row[4 + k];
+  }
+  const float lo = lohi[0], hi = lohi[1];
+  const float share_lo = row[0] / row[2], share_hi = row[1] / row[3];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float x = raw[3 * i];
+    out[3 * i] = (out[3 * i] + ((x == hi) ? share_hi : 0.0f)) + ((x == lo) ? share_lo : 0.0f);
+  }
+}
+#endif
 
 // workspace: words 0-2 global min / max / NaN flag, the rest zero (tile queue counters)
 __global__ void k_minmax_init(uint32_t* mm) {

@@ -36,6 +36,16 @@ def tile_payload(tile: torch.Tensor, mode: int) -> torch.Tensor:
     return tile[..., :1].contiguous() if grey else tile.contiguous()
 
 
+def _takes_minmax(mode) -> bool:
+    """Whether a frame of ``mode`` all-reduces a min / max between its two passes: the built-in modes 1, 2 and 5, and a user shader
+    registered with ``normalise="minmax"``."""
+    if isinstance(mode, torch.nn.Module):
+        from .extensions import shader_spec
+        spec = shader_spec(mode)
+        return spec is not None and spec.normalise is not None
+    return mode % 8 in (1, 2, 5)
+
+
 def expand_payload(frame: torch.Tensor) -> torch.Tensor:
     """[N,H,W,1] -> the [N,H,W,3] view the reference's Shader.forward returns; 3-channel frames pass."""
     return frame.expand(-1, -1, -1, 3) if frame.shape[-1] == 1 else frame
@@ -163,7 +173,7 @@ class RowTileRenderer:
             # surplus rank: nothing to render, but it takes part in every exchange (incl. the min/max all-reduce);
             # everything it needs is known BEFORE the first collective, so it cannot fail while the others wait
             tile = self._empty_tile(like)
-            if not isinstance(mode, torch.nn.Module) and mode % 8 in (1, 2, 5):
+            if _takes_minmax(mode):
                 lohi = torch.tensor([float("inf"), float("-inf")], device=tile.device)
                 self._allreduce_minmax(lohi)
         tile = tile_payload(tile, mode)

@@ -121,6 +121,24 @@ earlier values before their own scene VJP runs (K <= 8: the whole chain is in re
 per probe through constant indices precisely so that no array is ever indexed with it.  The class's PyTorch ``forward(..., scene)``
 needs nothing new: it calls ``scene`` in sequence and autograd does the rest.
 
+*Frame-normalised shaders* depend on a statistic of the whole frame: ``register_shader(..., normalise="minmax")`` (orthogonal to
+``probes=`` and ``chained=``).  What ``NAME_fwd`` returns is then the RAW triple of the pixel, not its colour; the frame takes ``lo =
+min raw.x`` and ``hi = max raw.x`` over every pixel of every camera (a NaN anywhere makes both NaN, as ``torch.min`` / ``torch.max``
+do; ``raw.y`` and ``raw.z`` ride along untouched), and a second pass maps every pixel through a pair the source brings as well,
+
+    template <bool Fast> RM_DEV rm::V3 NAME_finish    (rm::V3 raw, float lo, float hi, const float* theta);
+    template <bool Fast> RM_DEV void   NAME_finish_vjp(rm::V3 raw, float lo, float hi, const float* theta, rm::V3 g,
+                                                       rm::V3& graw, float& glo, float& ghi, float* gtheta);
+
+``theta`` is the vector ``NAME_fwd`` sees; the VJP WRITES all four outputs (they arrive zeroed): ``graw = dL/d(raw)`` through the
+pixel's own value, ``glo`` / ``ghi`` the pixel's share of ``dL/dlo`` / ``dL/dhi``, ``gtheta[i]`` its share of ``dL/dtheta_i``.  The kernels
+sum ``glo``, ``ghi`` and ``gtheta`` over the frame (in a fixed order: two backwards give the same bits), hand ``sum glo / n_lo`` to every
+pixel with ``raw.x == lo`` and ``sum ghi / n_hi`` to every pixel with ``raw.x == hi`` -- ties share evenly, as autograd's ``min()`` /
+``max()`` do -- and pass the completed ``graw`` to ``NAME_vjp`` as its ``g``.  The PyTorch ``forward`` needs nothing new: it calls ``.min()`` /
+``.max()`` on its own tensor.  A backward through a minimum / maximum taken across ranks (``rows=`` with ``allreduce_minmax``) raises
+NotImplementedError, as for the built-in distance, proximity and Laplacian modes; a frame with ``lo == hi`` is whatever
+``NAME_finish`` makes of it.
+
 Scenes that contain such a leaf, combinator or warp, and frames shaded by such a shader, run only through their per-scene specialised library (specialize.py), into which
 the source is compiled; the LDS interpreter has no handler for them and ``CompiledScene.lib()`` says so instead of
 rendering a wrong picture.
@@ -180,6 +198,7 @@ class UserShader(_UserSpec):
     sha1: str
     probes: int = 0     # K: the scene evaluations the shader asks for per pixel (NAME_probe / NAME_probe_vjp); 0: none
     chained: bool = False   # probe k may depend on the values of the probes before it (the pair takes the history h / gh)
+    normalise: object = None    # "minmax": NAME_fwd returns the raw triple, NAME_finish / NAME_finish_vjp map it through the frame's min / max
 
 
 @dataclass(frozen=True)
@@ -197,6 +216,7 @@ class _Kind:
     out_pair: bool = False          # the source may bring NAME_out_fwd / NAME_out_vjp
     bound: str = ""                 # the noun under which NAME_bound is looked for ("": the kind signs no bound)
     probe_pair: bool = False        # the source may bring NAME_probe / NAME_probe_vjp (a shader's scene probes)
+    finish_pair: bool = False       # the source may bring NAME_finish / NAME_finish_vjp (a shader normalised by the frame's min / max)
 
 
 _KINDS = {
@@ -225,9 +245,10 @@ _KINDS = {
         "`template <bool Fast> RM_DEV void NAME_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 g, rm::ShadeGrad& gs, float* "
         "gtheta)`",
         methods=(("forward", "forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals)"),),
-        same=("sha1", "params", "probes", "chained"), device_forward=False, probe_pair=True),
+        same=("sha1", "params", "probes", "chained", "normalise"), device_forward=False, probe_pair=True, finish_pair=True),
 }
 
+NORMALISATIONS = (None, "minmax")    # register_shader(normalise=...): the frame statistics a shader may be normalised by
 RM_USER_SHADER_MAX_PROBES = 8       # the most scene probes a shader may ask for (d[] / gd[] live in registers: INTEGRATION.md)
 
 _registry: dict[type, _UserSpec] = {}       # registered class -> its registration, of whichever kind
@@ -236,10 +257,10 @@ _DEF = r"\b([A-Za-z_]\w*)_%s\s*\("
 
 
 def _parse(kind: str, hip: str):
-    """(NAME, has_out, bounded, has_probe) of the source of a ``kind``.  NAME is that of the one ``NAME_fwd`` with the kind's return
+    """(NAME, has_out, bounded, has_probe, has_finish) of the source of a ``kind``.  NAME is that of the one ``NAME_fwd`` with the kind's return
     type and must be that of the ``NAME_vjp`` too (of one of them where the kind may bring ``NAME_out_fwd`` / ``NAME_out_vjp``, which
     come as a pair or not at all and are looked up by their full names, like NAME_bound).  A shader's ``NAME_probe`` /
-    ``NAME_probe_vjp`` are such a pair too: ``NAME_probe_vjp`` is no second shader."""
+    ``NAME_probe_vjp`` are such a pair too: ``NAME_probe_vjp`` is no second shader; so are its ``NAME_finish`` / ``NAME_finish_vjp``."""
     row = _KINDS[kind]
     text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
 
@@ -252,6 +273,10 @@ def _parse(kind: str, hip: str):
     if row.probe_pair and name is not None:
         probe_fwd, probe_vjp = name in names(row.ret, "probe"), f"{name}_probe" in vjp
         vjp = vjp - {f"{name}_probe"}
+    finish_fwd = finish_vjp = False
+    if row.finish_pair and name is not None:
+        finish_fwd, finish_vjp = name in names(row.ret, "finish"), f"{name}_finish" in vjp
+        vjp = vjp - {f"{name}_finish"}
     if name is None or (name not in vjp if row.out_pair else vjp != fwd):
         raise ValueError(f"hip must define {row.signature}, with one NAME (found fwd: {sorted(fwd)}"
                          + ("" if row.out_pair else f", vjp: {sorted(vjp)}") + ")")
@@ -266,7 +291,12 @@ def _parse(kind: str, hip: str):
         raise ValueError(f"hip may define `template <bool Fast> RM_DEV rm::V3 {name}_probe(int k, const rm::ShadeIn& s, const float* theta)` "
                          f"and `template <bool Fast> RM_DEV void {name}_probe_vjp(int k, const rm::ShadeIn& s, const float* theta, rm::V3 gq, "
                          f"rm::ShadeGrad& gs, float* gtheta)`: both or neither (found {name}_probe: {probe_fwd}, {name}_probe_vjp: {probe_vjp})")
-    return name, out_fwd, bool(row.bound) and _has_bound(text, name, row.bound), probe_fwd
+    if finish_fwd != finish_vjp:
+        raise ValueError(f"hip may define `template <bool Fast> RM_DEV rm::V3 {name}_finish(rm::V3 raw, float lo, float hi, const float* theta)` "
+                         f"and `template <bool Fast> RM_DEV void {name}_finish_vjp(rm::V3 raw, float lo, float hi, const float* theta, rm::V3 g, "
+                         f"rm::V3& graw, float& glo, float& ghi, float* gtheta)`: both or neither (found {name}_finish: {finish_fwd}, "
+                         f"{name}_finish_vjp: {finish_vjp})")
+    return name, out_fwd, bool(row.bound) and _has_bound(text, name, row.bound), probe_fwd, finish_fwd
 
 
 def _has_bound(text: str, name: str, what: str) -> bool:
@@ -341,7 +371,7 @@ def _register(kind: str, cls, *, params, hip: str, **own):
     params = tuple(params)
     if not all(isinstance(p, str) for p in params) or len(set(params)) != len(params):
         raise ValueError(f"{fn}: params must be distinct attribute names")
-    name, has_out, bounded, has_probe = _parse(kind, hip)
+    name, has_out, bounded, has_probe, has_finish = _parse(kind, hip)
     if row.probe_pair:
         probes = own["probes"]
         if isinstance(probes, bool) or not isinstance(probes, int) or not 0 <= probes <= RM_USER_SHADER_MAX_PROBES:
@@ -356,6 +386,14 @@ def _register(kind: str, cls, *, params, hip: str, **own):
         if chained and probes < 2:
             raise ValueError(f"{fn}: chained=True needs probes from 2 to RM_USER_SHADER_MAX_PROBES = {RM_USER_SHADER_MAX_PROBES} (a chain of "
                              f"one probe has no history), not probes={probes}")
+    if row.finish_pair:
+        normalise = own["normalise"]
+        if normalise not in NORMALISATIONS:
+            raise ValueError(f"{fn}: normalise must be None or \"minmax\", not {normalise!r}")
+        if has_finish and normalise is None:
+            raise ValueError(f"{fn}: the source of {cls.__name__} defines {name}_finish / {name}_finish_vjp, but normalise=None")
+        if normalise is not None and not has_finish:
+            raise ValueError(f"{fn}: normalise={normalise!r}, but the source of {cls.__name__} defines no {name}_finish / {name}_finish_vjp")
     if row.out_pair and has_out != callable(getattr(cls, "out", None)):
         raise TypeError(f"{fn}: {cls.__name__} " + (
             f"has no out(values, points) method, but its source defines {name}_out_fwd / {name}_out_vjp" if has_out else
@@ -374,7 +412,9 @@ def _register(kind: str, cls, *, params, hip: str, **own):
         if any(getattr(old, f) != getattr(spec, f) for f in row.same):
             raise ValueError(f"{fn}: {cls.__name__} is already registered with different {row.different}"
                              + (" (or another number of probes)" if row.probe_pair and old.probes != spec.probes else "")
-                             + (f" (chained={old.chained} before, chained={spec.chained} now)" if row.probe_pair and old.chained != spec.chained else ""))
+                             + (f" (chained={old.chained} before, chained={spec.chained} now)" if row.probe_pair and old.chained != spec.chained else "")
+                             + (f" (normalise={old.normalise!r} before, normalise={spec.normalise!r} now)"
+                                if row.finish_pair and old.normalise != spec.normalise else ""))
         return cls
     for other in _registry.values():
         if other.name == spec.name:          # (a scene's user types and the shader are compiled into one translation unit)
@@ -470,7 +510,7 @@ def warp_child(node, spec: UserWarp):
     return kid
 
 
-def register_shader(cls, *, params=(), hip: str, probes: int = 0, chained: bool = False):
+def register_shader(cls, *, params=(), hip: str, probes: int = 0, chained: bool = False, normalise=None):
     """Make instances of ``cls`` (an ``nn.Module`` subclass) usable as the ``mode`` of ``RenderLoop.forward``: a per-pixel shader
     that runs fused at the end of the frame kernels and in the fused backward.
 
@@ -484,12 +524,15 @@ def register_shader(cls, *, params=(), hip: str, probes: int = 0, chained: bool 
             history ``const float* h`` behind theta (the VJP also ``float* gh`` at its end), K-1 entries relative to ``k``, ``h[0]`` the
             most recent value, zeros where there is none yet; index ``h`` / ``gh`` / ``d`` / ``gd`` with constants only (module docstring:
             "chained probes").
+    normalise: None (the default: ``NAME_fwd`` returns the pixel's colour), or "minmax": ``NAME_fwd`` returns the pixel's raw triple, the
+            frame takes ``lo = min raw.x`` / ``hi = max raw.x`` over all pixels of all cameras, and the source brings NAME_finish /
+            NAME_finish_vjp, which make the colour of ``(raw, lo, hi, theta)`` (module docstring: "frame-normalised shaders").
 
     ``cls`` has ``forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals) -> [..., 3]``,
     the first six arguments of the reference's ``Shader.forward`` (``camera_orientation`` [N,4], ``pixel_frames`` [N,3,3]); it is
     the CPU statement of the shader and is NOT replaced.  Registering a class again with the same source is a no-op; with other
-    source, parameters, number of probes or value of ``chained`` it is an error.  Identifiers are unique across all four kinds (leaves, combinators, warps and shaders)."""
-    return _register("shader", cls, params=params, hip=hip, probes=probes, chained=chained)
+    source, parameters, number of probes or value of ``chained`` / ``normalise`` it is an error.  Identifiers are unique across all four kinds (leaves, combinators, warps and shaders)."""
+    return _register("shader", cls, params=params, hip=hip, probes=probes, chained=chained, normalise=normalise)
 
 
 def shader_spec(node):

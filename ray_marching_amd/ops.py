@@ -421,6 +421,25 @@ def minmax_normalisation_vjp(grad_image: torch.Tensor, logd: torch.Tensor, lo: t
     return ga + torch.where(top, gr / top.sum(), zero) + torch.where(bottom, gm / bottom.sum(), zero)
 
 
+def frame_minmax_vjp(graw_x: torch.Tensor, glo: torch.Tensor, ghi: torch.Tensor, x: torch.Tensor, lo: torch.Tensor,
+                     hi: torch.Tensor) -> torch.Tensor:
+    """VJP of ``lo = x.min()`` / ``hi = x.max()`` over a frame, as the second pass of a user shader registered with
+    ``normalise="minmax"`` needs it (rm_user_shade_norm_backward; this is its readable statement): ``graw_x`` is dL/dx through every
+    pixel's own value, ``glo`` / ``ghi`` (0-dim) are dL/dlo and dL/dhi, already summed over the frame.  The two end terms go to the
+    pixels that attain the extremum, shared evenly among ties, as autograd's ``min()`` / ``max()`` share them.  They are selects: in a
+    frame with a NaN (``lo`` and ``hi`` are NaN then) no pixel compares equal and none takes a share, where autograd hands them to
+    the NaN pixels -- whose upstream is NaN either way."""
+    bottom, top = x == lo, x == hi
+    zero = torch.zeros_like(graw_x)
+    return (graw_x + torch.where(top, ghi / top.sum(), zero)) + torch.where(bottom, glo / bottom.sum(), zero)
+
+
+def user_normalised(cs, mode) -> bool:
+    """Whether ``mode`` on the program ``cs`` is a user shader normalised by the frame's min / max (register_shader(normalise="minmax")):
+    a frame of two passes, like modes 1, 2 and 5."""
+    return mode == _abi.MODE_USER and cs.user_shader_normalise is not None
+
+
 def laplacian_normalisation_vjp(grad_image: torch.Tensor, lap: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
     """VJP of LaplacianShader's normalisation (shader.py:81-89: lap / lap.abs().max() * -1 + 1, / 2, clamp(0, 1),
     pow(1 / 2.33), expanded to three channels) in the order autograd walks it; returns dL/d(surface_laplacian)
@@ -509,7 +528,8 @@ class Render(torch.autograd.Function):
             else torch.empty((n, nrows, w, 3), dtype=image_dtype, device=dev)
         image_code = _abi.DTYPE_RGBA_F32 if rgba else _abi.dtype_code(image_dtype)
         first_pass = None
-        if mode in _GLOBAL_MODES:
+        user_norm = user_normalised(cs, mode)
+        if mode in _GLOBAL_MODES or user_norm:
             # (a training frame of the Laplacian shader keeps the un-normalised values for its backward)
             first_pass = image if (image_dtype == torch.float32 and not record) \
                 else torch.empty((n, nrows, w, 3), dtype=torch.float32, device=dev)
@@ -561,15 +581,19 @@ class Render(torch.autograd.Function):
                 if event_sink is None:
                     globals()["fwd_last_work"] = minmax   # measurement runs (kernel_event_sink): the workspace words of this frame
             lohi = None
-            if mode in _GLOBAL_MODES:
+            if mode in _GLOBAL_MODES or user_norm:
                 if allreduce_minmax is not None or record:
                     lohi = torch.empty(2, dtype=torch.float32, device=dev)
                     _abi.check(_lib.rm_minmax_decode(_abi.ptr(minmax), _abi.ptr(lohi), stream), "rm_minmax_decode")
                 if allreduce_minmax is not None:
                     allreduce_minmax(lohi)
                     _abi.check(_lib.rm_minmax_encode(_abi.ptr(lohi), _abi.ptr(minmax), stream), "rm_minmax_encode")
-                _abi.check(_lib.rm_shade_finish(_abi.ptr(first_pass), _abi.ptr(image), image_code,
-                                                n * nrows * w, _abi.ptr(minmax), mode, _abi.dtype_code(rp.dtype), stream), "rm_shade_finish")
+                if user_norm:       # NAME_finish, compiled into the program's own library (the generic one answers with an error)
+                    _abi.check(lib.rm_user_shade_finish(s, _abi.ptr(first_pass), _abi.ptr(image), image_code, n * nrows * w,
+                                                        _abi.ptr(minmax), _abi.dtype_code(rp.dtype), stream), "rm_user_shade_finish", lib)
+                else:
+                    _abi.check(_lib.rm_shade_finish(_abi.ptr(first_pass), _abi.ptr(image), image_code,
+                                                    n * nrows * w, _abi.ptr(minmax), mode, _abi.dtype_code(rp.dtype), stream), "rm_shade_finish")
         if ctx is not None:
             ctx.have_vjp = have_vjp
             ctx.mode = mode
@@ -578,7 +602,8 @@ class Render(torch.autograd.Function):
             # (the backward kernels read the live storages, which must still hold the forward's values)
             ctx.save_for_backward(prm, q, t, rp, rd, p_final, traj, nexec, normal_u, *leaves)
             # Laplacian shader: the un-normalised values and their largest magnitude, for the normalisation's VJP
-            ctx.lap = (first_pass, lohi, allreduce_minmax is not None) if mode in _GLOBAL_MODES else None
+            ctx.lap = (first_pass, lohi, allreduce_minmax is not None) if (mode in _GLOBAL_MODES or user_norm) else None
+            ctx.user_norm = user_norm
             ctx.scene_keep = keep       # (program, packed block or None, pointer table or None): what backward reads through
             ctx.cs, ctx.tetra, ctx.steps, ctx.rows, ctx.flags = cs, tetra, steps, (r0, r1), flags
             ctx.precision, ctx.cmap, ctx.degree = precision, cmap, degree
@@ -593,7 +618,27 @@ class Render(torch.autograd.Function):
         prm, q, t, rp, rd, p_final, traj, nexec, normal_u, *leaves = ctx.saved_tensors
         cs, dev = ctx.cs, rp.device
         g = _f32c(grad_image)
-        if ctx.mode in _GLOBAL_MODES:
+        gtheta = None
+        if ctx.user_norm:
+            # the second pass of a user shader normalised by the frame's min / max: NAME_finish_vjp per pixel, the frame sums of
+            # dL/dlo, dL/dhi and dL/dtheta, and the two end terms back to the pixels that attain them (frame_minmax_vjp above is
+            # its statement); NAME_vjp then takes the result as its upstream, and the P sums join the shader's gradient below
+            raw3, lohi, across_ranks = ctx.lap
+            if across_ranks:
+                raise NotImplementedError("gradient of a globally normalised shader through a minimum / maximum taken across ranks")
+            floats = cs.user_shader[1]
+            graw3 = torch.empty_like(raw3)
+            gtheta = torch.empty(max(floats, 1), dtype=torch.float32, device=dev)
+            part = torch.empty(_abi.NORM_BWD_BLOCKS * (4 + floats), dtype=torch.float32, device=dev)
+            lib = cs.lib(True, ctx.precision)
+            with torch.cuda.device(dev):
+                s, keep = cs.scene_struct(prm if prm is not None else ctx.scene_keep[1], dev, table=ctx.scene_keep[2],
+                                          block=ctx.scene_keep[4] if use_forward_block else None)
+                _abi.check(lib.rm_user_shade_norm_backward(s, _abi.ptr(raw3), _abi.ptr(g), _abi.ptr(lohi), _abi.ptr(graw3),
+                                                           _abi.ptr(gtheta), _abi.ptr(part), raw3.numel() // 3,
+                                                           _abi.current_stream(dev)), "rm_user_shade_norm_backward", lib)
+            g = graw3
+        elif ctx.mode in _GLOBAL_MODES:
             # the normalisation over the whole frame is differentiated here; the kernels take dL/d(un-normalised value)
             raw3, lohi, across_ranks = ctx.lap
             if across_ranks:
@@ -640,6 +685,8 @@ class Render(torch.autograd.Function):
                                                ctx.flags & ~bwd_clear_flags,
                                                _abi.ptr(bwd_tile_cost_sink), _abi.ptr(hard), hard_cap, stream),
                        "rm_render_backward", lib)
+        if gtheta is not None and cs.user_shader[1]:
+            gprm[cs.shader_offset:cs.shader_offset + cs.user_shader[1]] += gtheta[:cs.user_shader[1]]
         gq = gt = None
         if need_pose:
             gq, gt = _camera_backward(rp, rd, q, gpos, gdirs, ctx.rows, ctx.needs_input_grad[1], ctx.needs_input_grad[2])

@@ -174,7 +174,24 @@ def _shader_section(cs: CompiledScene) -> str:
     """The user shader's source and the functions the frame kernels call, for the header's inclusion from csrc/rm_kernels.h
     (behind rm::ShadeIn / rm::ShadeGrad, inside namespace rm): two, or -- a shader with scene probes, RM_USER_SHADER_PROBES --
     four, of which user_shader_fwd / user_shader_vjp then carry the probe values; the probe pair of a chained shader
-    (RM_USER_SHADER_PROBES_CHAINED) also carries the history ``h`` of the values before probe ``k`` and, in the VJP, ``gh``."""
+    (RM_USER_SHADER_PROBES_CHAINED) also carries the history ``h`` of the values before probe ``k`` and, in the VJP, ``gh``.  A shader
+    normalised by the frame's min / max (RM_USER_SHADER_NORMALISE) adds user_shader_finish / user_shader_finish_vjp, the second
+    pass; every other header is, byte for byte, what it was without them."""
+    text = _shader_passes(cs)
+    if not cs.user_shader_normalise:
+        return text
+    name = cs.user_shader[0]
+    return (
+        "#define RM_USER_SHADER_NORMALISE 1\n" + text +
+        "template <bool Fast> RM_DEV V3 user_shader_finish(V3 raw, float lo, float hi, const float* theta) {\n"
+        f"  return {name}_finish<Fast>(raw, lo, hi, theta);\n}}\n"
+        "template <bool Fast> RM_DEV void user_shader_finish_vjp(V3 raw, float lo, float hi, const float* theta, V3 g, V3& graw, float& glo, "
+        "float& ghi, float* gtheta) {\n"
+        f"  {name}_finish_vjp<Fast>(raw, lo, hi, theta, g, graw, glo, ghi, gtheta);\n}}\n")
+
+
+def _shader_passes(cs: CompiledScene) -> str:
+    """The shader section without the second pass: the source, and the forwarders of the per-pixel pair and of the probe pair."""
     name, floats, sha = cs.user_shader
     k = cs.user_shader_probes
     head = ("#define RM_USER_SHADER 1\n"
