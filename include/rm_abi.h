@@ -188,7 +188,8 @@ enum {
                               rm_user_shaders() == 1 and refused by every other; rm_shade_forward / rm_shade_backward, which have no
                               scene and hence no theta, never take it.  Per pixel, [.., 3] like the other ungrouped modes (no global
                               normalisation, no colormap -- unless the shader was registered with normalise="minmax":
-                              rm_user_shade_finish below); the frame evaluates neither the Laplacian nor scene(p) for it */
+                              rm_user_shade_finish below -- and unless it reads a lookup table, which then travels in the colormap
+                              arguments: rm_user_shader_table below); the frame evaluates neither the Laplacian nor scene(p) for it */
 };
 
 /* flags */
@@ -454,6 +455,31 @@ int rm_user_shade_finish(const RmScene* scene, const float* first_pass, void* im
                          const uint32_t* minmax, int32_t round_dtype, void* stream);
 int rm_user_shade_norm_backward(const RmScene* scene, const float* raw, const float* grad_image, const float* lohi /*device [2]*/,
                                 float* grad_raw, float* grad_theta, float* partials, int64_t n_pixels, void* stream);
+
+/* A user shader with a lookup table (extensions.register_shader(table=..., table_taps=T)): the library of such a (scene, shader)
+ * pair reports T from rm_user_shader_table() (every other library 0).  The table -- float32 [L,3], 2 <= L <= RM_TABLE_MAX_ROWS,
+ * read in place -- travels in the colormap slot: for RM_MODE_USER its rm_render_forward and rm_render_backward REQUIRE cmap != NULL,
+ * cmap_dtype == RM_DTYPE_F32 and 2 <= cmap_size <= RM_TABLE_MAX_ROWS and answer RM_E_BADARG (no launch) otherwise.
+ * rm_render_backward_table: rm_render_backward with one more output, the table's gradient records -- nullable; NULL is
+ * rm_render_backward itself.  table_records: [R][T][4] floats, 16-byte aligned, R = num_cameras * rows * width: for pixel r and
+ * tap k the bit pattern of the int32 row (clamped to [0, L-1]; -1: no contribution) and dL/d(that row).  Every record of the band is
+ * written.  Libraries without a table answer a non-NULL table_records with RM_E_BADARG.
+ * rm_table_scatter (every library): grad_table[L][3] = the sum of the records per row; rows outside [0, L) contribute nothing,
+ * rows no record names get exactly 0.  No float atomics; the order of every sum depends on the record index alone (one wave per
+ * RM_TABLE_CHUNK consecutive records, then rm_sum_rows' tree over the chunks): the same records give the same bits.
+ * partials: ((n_records + RM_TABLE_CHUNK - 1) / RM_TABLE_CHUNK) * 3 * L floats. */
+#define RM_TABLE_MAX_ROWS 4096
+#define RM_TABLE_CHUNK 2048
+int rm_user_shader_table(void);
+int rm_render_backward_table(const RmScene* scene, const RmCamera* cam, const RmTetra* tetra,
+                             const float* orientation, const float* translation,
+                             const float* traj, const int32_t* nexec, const float* p_final, const float* normal_u,
+                             const float* grad_image, float* grad_params, float* partials, uint32_t* work,
+                             float* grad_pos, float* grad_dirs, float* grad_qdir,
+                             const void* cmap, int32_t cmap_size, int32_t cmap_dtype,
+                             int32_t mode, int32_t degree, int32_t steps, int32_t row_begin, int32_t row_end, int32_t flags,
+                             int32_t* tile_cost, float* hard_ws, int64_t hard_capacity, float* table_records, void* stream);
+int rm_table_scatter(const float* records, int64_t n_records, int32_t table_rows, float* grad_table, float* partials, void* stream);
 
 /* out[width] = sum over n_rows rows of rows[n_rows][width], fixed summation tree (deterministic). */
 int rm_sum_rows(const float* rows, int64_t n_rows, int32_t width, float* out, void* stream);

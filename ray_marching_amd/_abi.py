@@ -45,6 +45,8 @@ def dtype_code(dtype) -> int:
 WORK_WORDS = 64 + 64 * 32 + 8 * 4 * 32 + 64 * 32   # RM_WORK_WORDS (min/max words, tile queues, parking counters, min/max slots)
 CAMERA_BWD_BLOCKS = 256     # RM_CAMERA_BWD_BLOCKS
 NORM_BWD_BLOCKS = 1024      # RM_NORM_BWD_BLOCKS
+TABLE_CHUNK = 2048          # RM_TABLE_CHUNK: records one wave of k_table_scatter owns
+TABLE_MAX_ROWS = 4096       # RM_TABLE_MAX_ROWS
 MODE_USER = 8               # RM_MODE_USER: a user-defined shader (extensions.register_shader); not one of MODES
 MODES = ("lambertian", "distance", "proximity", "vignette", "normal", "laplacian", "tangent", "spin")
 
@@ -77,6 +79,7 @@ _SIGNATURES = {
     "rm_user_combinators": (C.c_int, []),
     "rm_user_warps": (C.c_int, []),
     "rm_user_shaders": (C.c_int, []),
+    "rm_user_shader_table": (C.c_int, []),
     "rm_grad_partials_floats": (C.c_int64, [C.POINTER(RmScene), C.c_int64]),
     "rm_validate_program": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rm_sdf_forward": (C.c_int, [C.POINTER(RmScene), _P, _P, C.c_int64, C.c_int32, _P]),
@@ -107,6 +110,11 @@ _SIGNATURES = {
                                      _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                      _P, _P, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
+    "rm_render_backward_table": (C.c_int, [C.POINTER(RmScene), C.POINTER(RmCamera), C.POINTER(RmTetra), _P, _P,
+                                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P]),
+    "rm_table_scatter": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P]),
     "rm_sum_rows": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P]),
     "rm_shade_norm_backward": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int64, _P]),
     "rm_user_shade_finish": (C.c_int, [C.POINTER(RmScene), _P, _P, C.c_int32, C.c_int64, _P, C.c_int32, _P]),

@@ -116,6 +116,8 @@ class CompiledScene:
     user_shader_probes: int = 0         # K: the scene probes it asks for per pixel (register_shader(probes=K)); 0: none
     user_shader_chained: bool = False   # its probes take the history of the values before them (register_shader(chained=True))
     user_shader_normalise: object = None    # "minmax": its NAME_fwd returns a raw triple that NAME_finish maps through the frame's min / max
+    user_shader_table: str = ""         # the attribute that holds its lookup table (register_shader(table=...)); "": none
+    user_shader_table_taps: int = 0     # T: the most table rows one pixel's VJP contributes to; 0: no table
     shader_offset: int = 0              # where its theta starts in the block (= the scene's own n_params)
     _device_programs: dict = field(default_factory=dict)
     _table: dict = field(default_factory=dict)
@@ -485,6 +487,7 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
         table[id(p)] = cursor
         cursor += p.numel()
     shader_offset, user_shader, shader_source, shader_probes, shader_chained, shader_normalise = cursor, (), "", 0, False, None
+    shader_table, shader_table_taps = "", 0
     if shader is not None:
         spec = shader_spec(shader)
         if spec is None:
@@ -498,6 +501,7 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
             cursor += p.numel()
         user_shader, shader_source, shader_probes = (spec.name, cursor - shader_offset, spec.sha1), spec.hip, spec.probes
         shader_chained, shader_normalise = spec.chained, spec.normalise
+        shader_table, shader_table_taps = spec.table, spec.table_taps
     n_params = cursor                 # (derived constants start behind the shader's floats)
     em = _Emitter(table)
     # derived block = [capsule constants of every SDFLine (gradients flow through them) | cull bounds, bound tables]
@@ -524,6 +528,8 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
         slots.append(("chained",))
     if shader_normalise:              # (... and so is one normalised by the frame's min / max: its header brings the second pass)
         slots.append(("normalise", shader_normalise))
+    if shader_table:                  # (... and one that reads a lookup table: its pair takes tab / gt.  L and the values stay run-time)
+        slots.append(("table", shader_table, shader_table_taps))
     signature = (tuple(map(tuple, program.tolist())), n_params, em.n_derived, em.max_depth, em.n_slots, em.n_grad_derived, *slots)
     return CompiledScene(program=program, leaves=leaves, leaf_names=names, leaf_offsets=offsets,
                          n_params=n_params, n_derived=em.n_derived, n_grad_derived=em.n_grad_derived, stack_floats=em.max_depth,
@@ -535,7 +541,8 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
                          user_warp_bounded=tuple(u.bounded for u, _ in warp_types),
                          user_shader=user_shader, user_shader_source=shader_source, shader_offset=shader_offset,
                          user_shader_probes=shader_probes, user_shader_chained=shader_chained,
-                         user_shader_normalise=shader_normalise)
+                         user_shader_normalise=shader_normalise, user_shader_table=shader_table,
+                         user_shader_table_taps=shader_table_taps)
 
 
 def structure_key(module: nn.Module):

@@ -3,6 +3,8 @@
 PyTorch ``forward`` / ``combine`` / ``warp`` (the CPU path and the oracle) and the same op stream in HIP."""
 from __future__ import annotations
 
+import math
+
 import torch
 import torch.nn as nn
 from torch import Tensor
@@ -998,3 +1000,143 @@ template <bool Fast> RM_DEV void depth_ramp_finish_vjp(rm::V3 raw, float lo, flo
 """
 
 register_shader(DepthRampShader, params=("near_colour", "far_colour", "clip_near", "clip_far"), hip=_DEPTH_RAMP_HIP, normalise="minmax")
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# Shaders that read a lookup table (register_shader(table=..., table_taps=T)): storage a shader may index at run time, and
+# whose rows take gradients through a deterministic scatter
+# --------------------------------------------------------------------------------------------------------------------
+class TangentPaletteShader(nn.Module):
+    """The built-in tangent mode (mode 6 at degree 1) restated as a user shader: the normal's tangential part, rotated into the
+    camera frame, colours the pixel with ``brightness * palette[floor((atan2(im, re) / tau + 0.5) * L) mod L]``.  The ``palette`` ([L, 3]
+    float32, ``2 <= L <= 4096``) is a Parameter: where the built-in mode reads a fixed colormap, this one learns its rows (one row
+    per pixel: ``table_taps=1``).  No ``theta``."""
+
+    def __init__(self, palette) -> None:
+        super().__init__()
+        self.palette = nn.Parameter(torch.as_tensor(palette, dtype=torch.float32).clone().contiguous())
+
+    def forward(self, px_coords: Tensor, camera_orientation: Tensor, pixel_frames: Tensor, ray_directions: Tensor,
+                surface_coords: Tensor, surface_normals: Tensor) -> Tensor:
+        from .quaternion import conjugate, rotation
+        n, v = surface_normals, ray_directions
+        tangential = ((n * v).sum(dim=-1, keepdim=True) * v) * (-1.0) + n
+        proj = rotation(tangential, conjugate(camera_orientation)[:, None, None, :])
+        re, im = proj[..., 0], proj[..., 1]
+        bright = torch.stack((re, im), dim=-1).pow(2).sum(dim=-1, keepdim=True).pow(1 / 2)
+        size = self.palette.shape[0]
+        idx = (torch.atan2(im, re) / math.tau + 0.5) * 1 * size
+        return bright * self.palette[idx.floor().long().remainder(size), :]
+
+
+# the forward is shade_pixel's RM_MODE_TANGENT case and domain_colour, the VJP shade_pixel_vjp's tangent branch, op for op; the row
+# index is piecewise constant (no gradient through it), the row itself takes brightness * g
+_TANGENT_PALETTE_HIP = r"""
+template <bool Fast> RM_DEV rm::V3 tangent_palette_fwd(const rm::ShadeIn& s, const float* theta, const rm::Table& tab) {
+  const float c = dot_seq(s.n, s.v);
+  const rm::V3 tg = mk3((c * s.v.x) * -1.0f + s.n.x, (c * s.v.y) * -1.0f + s.n.y, (c * s.v.z) * -1.0f + s.n.z);
+  const rm::V3 pr = qrot(tg, s.qw, neg(s.qv));
+  const rm::Shaded sh = domain_colour(pr.x, pr.y, tab.n, 1);
+  const rm::V3 row = tab.row(sh.idx);
+  return mk3(sh.bright * row.x, sh.bright * row.y, sh.bright * row.z);
+}
+template <bool Fast> RM_DEV void tangent_palette_vjp(const rm::ShadeIn& s, const float* theta, const rm::Table& tab, rm::V3 g,
+                                                     rm::ShadeGrad& gs, float* gtheta, rm::TableGrad& gt) {
+  const float c = dot_seq(s.n, s.v);
+  const rm::V3 tg = mk3((c * s.v.x) * -1.0f + s.n.x, (c * s.v.y) * -1.0f + s.n.y, (c * s.v.z) * -1.0f + s.n.z);
+  const rm::V3 u = neg(s.qv);                 // rotation by conj(q): local = tg + w t + u x t, t = 2 u x tg
+  const rm::V3 pr = qrot(tg, s.qw, u);
+  const rm::Shaded sh = domain_colour(pr.x, pr.y, tab.n, 1);
+  const rm::V3 row = tab.row(sh.idx);
+  gt.row[0] = tab.clamp(sh.idx);
+  gt.g[0] = mk3(sh.bright * g.x, sh.bright * g.y, sh.bright * g.z);
+  const float gb = (g.x * row.x + g.y * row.y) + g.z * row.z;
+  const float gsq = gb * (0.5f / sh.bright);  // brightness = (re^2 + im^2).pow(1/2)
+  const rm::V3 gl = mk3(gsq * (2.0f * pr.x), gsq * (2.0f * pr.y), 0.0f);
+  const rm::V3 t = 2.0f * cross(u, tg);
+  const rm::V3 ugl = cross(u, gl);
+  const rm::V3 gtg = (gl + 2.0f * cross(u, ugl)) - (2.0f * s.qw) * ugl;
+  const rm::V3 gtt = s.qw * gl + cross(gl, u);
+  const rm::V3 gu = cross(t, gl) + 2.0f * cross(tg, gtt);
+  gs.qw += (gl.x * t.x + gl.y * t.y) + gl.z * t.z;
+  gs.qv = gs.qv - gu;
+  const float gtv = dot_seq(gtg, s.v);        // tg = n - (n.v) v
+  gs.n = gs.n + mk3(gtg.x - gtv * s.v.x, gtg.y - gtv * s.v.y, gtg.z - gtv * s.v.z);
+  gs.v = gs.v + mk3(-c * gtg.x - gtv * s.n.x, -c * gtg.y - gtv * s.n.y, -c * gtg.z - gtv * s.n.z);
+}
+"""
+
+register_shader(TangentPaletteShader, hip=_TANGENT_PALETTE_HIP, table="palette", table_taps=1)
+
+
+class DepthPaletteShader(nn.Module):
+    """A transfer function over depth: ``rgb = c * lerp(palette[i], palette[i + 1], u - i)`` with ``u = (L - 1) / (1 + density * |o - p|)``
+    (near: the last row, far: the first), ``i = min(floor(u), L - 2)`` and the Lambertian term ``c = clamp(-(v . n), 0, 1)``.  One
+    parameter float (``density``) and the ``palette`` ([L, 3] float32, a Parameter); gradients go to ``density``, the pose, the scene
+    and both rows (``table_taps=2``).  Continuous in ``u``; its slope jumps at the knots."""
+
+    def __init__(self, density: float = 0.25, palette=((0.1, 0.2, 0.5), (1.0, 0.9, 0.7))) -> None:
+        super().__init__()
+        self.density = nn.Parameter(torch.tensor(density, dtype=torch.float32))
+        self.palette = nn.Parameter(torch.as_tensor(palette, dtype=torch.float32).clone().contiguous())
+
+    def forward(self, px_coords: Tensor, camera_orientation: Tensor, pixel_frames: Tensor, ray_directions: Tensor,
+                surface_coords: Tensor, surface_normals: Tensor) -> Tensor:
+        c = (ray_directions * surface_normals).sum(dim=-1, keepdim=True).neg().clamp(0, 1)
+        dist = torch.linalg.vector_norm(px_coords - surface_coords, dim=-1, keepdim=True)
+        size = self.palette.shape[0]
+        u = (size - 1) * (self.density * dist + 1).reciprocal()
+        i = u.detach().floor().clamp(0, size - 2)
+        f = u - i
+        lo, hi = self.palette[i.long().squeeze(-1)], self.palette[i.long().squeeze(-1) + 1]
+        return c * (lo + f * (hi - lo))
+
+
+# theta = {density}
+_DEPTH_PALETTE_HIP = r"""
+template <bool Fast> RM_DEV rm::V3 depth_palette_fwd(const rm::ShadeIn& s, const float* theta, const rm::Table& tab) {
+  const float c = t_clamp(-dot_seq(s.v, s.n), 0.0f, 1.0f);
+  const float dist = norm3(s.o - s.p);
+  const float top = (float)(tab.n - 1);
+  const float u = top * (1.0f / (theta[0] * dist + 1.0f));
+  const float fi = t_clamp(floorf(u), 0.0f, top - 1.0f);
+  const float f = u - fi;
+  const int i = (int)fi;
+  const rm::V3 lo = tab.row(i), hi = tab.row(i + 1);
+  return mk3(c * (lo.x + f * (hi.x - lo.x)), c * (lo.y + f * (hi.y - lo.y)), c * (lo.z + f * (hi.z - lo.z)));
+}
+template <bool Fast> RM_DEV void depth_palette_vjp(const rm::ShadeIn& s, const float* theta, const rm::Table& tab, rm::V3 g,
+                                                   rm::ShadeGrad& gs, float* gtheta, rm::TableGrad& gt) {
+  const float e = -dot_seq(s.v, s.n);
+  const float c = t_clamp(e, 0.0f, 1.0f);
+  const rm::V3 d = s.o - s.p;
+  const float dist = norm3_t<Fast>(d);
+  const float top = (float)(tab.n - 1);
+  const float w = div_t<Fast>(1.0f, theta[0] * dist + 1.0f);
+  const float u = top * w;
+  const float fi = t_clamp(floorf(u), 0.0f, top - 1.0f);
+  const float f = u - fi;
+  const int i = (int)fi;
+  const rm::V3 lo = tab.row(i), hi = tab.row(i + 1);
+  const rm::V3 dl = hi - lo;
+  const rm::V3 mix = mk3(lo.x + f * dl.x, lo.y + f * dl.y, lo.z + f * dl.z);
+  const rm::V3 gm = c * g;                                    // dL/d(mix)
+  gt.row[0] = tab.clamp(i);     gt.g[0] = gm - f * gm;        // lo takes (1 - f), as autograd's lo + f * (hi - lo) hands it over
+  gt.row[1] = tab.clamp(i + 1); gt.g[1] = f * gm;
+  const float gf = (gm.x * dl.x + gm.y * dl.y) + gm.z * dl.z;
+  const float gw = gf * top;                                  // u = top * w; floor(u) carries no gradient
+  const float gup = -(gw * (w * w));                          // w = 1 / u', u' = density * dist + 1
+  gtheta[0] = gup * dist;
+  const float gdist = gup * theta[0];
+  const float sc = (dist == 0.0f) ? 0.0f : div_t<Fast>(gdist, dist);   // norm backward: self * (grad / norm), 0 where norm == 0
+  const rm::V3 gd = sc * d;
+  gs.o = gs.o + gd;
+  gs.p = gs.p - gd;
+  const float gc = (g.x * mix.x + g.y * mix.y) + g.z * mix.z;
+  const float ge = (e >= 0.0f && e <= 1.0f) ? gc : 0.0f;      // clamp passes the gradient on the closed interval
+  gs.v = gs.v - ge * s.n;
+  gs.n = gs.n - ge * s.v;
+}
+"""
+
+register_shader(DepthPaletteShader, params=("density",), hip=_DEPTH_PALETTE_HIP, table="palette", table_taps=2)

@@ -41,6 +41,15 @@ def resolve_mode(scene, mode, precision: str = "exact"):
     return _abi.MODE_USER, cs
 
 
+def _shader_table(cs, shader):
+    """The lookup table of a user shader registered with ``table=`` (the tensor itself: the kernels read it in place, so edits and
+    optimiser steps are simply what the next frame reads), or None."""
+    if not cs.user_shader_table:
+        return None
+    from .extensions import shader_spec, shader_table
+    return shader_table(shader, shader_spec(shader))
+
+
 class CapturedFrame:
     """One inference frame of a RenderLoop captured into a HIP graph (torch.cuda.CUDAGraph).
 
@@ -56,6 +65,7 @@ class CapturedFrame:
                  display: bool = False):
         """``display=True``: the replay writes main.py:78-84's display tensor ([H,W,4] fp32, alpha 1: RenderLoop.display_frame)
         instead of the [N,H,W,3] image (one camera)."""
+        shader = mode
         self.mode, self.cs = resolve_mode(loop.scene, mode, loop.precision)
         self.loop, self.degree, self.steps, self.rows = loop, int(degree), int(marching_steps), rows
         self.display = bool(display)
@@ -69,6 +79,11 @@ class CapturedFrame:
         with torch.no_grad():
             self.params = None if self.table is not None else self.cs.pack_params(dev).clone()
         cmap = loop._cmap(dev) if self.mode in (6, 7) else None
+        if self.mode == _abi.MODE_USER:       # (a user shader's lookup table: read in place, an in-place edit is seen by the next replay)
+            cmap = _shader_table(self.cs, shader)
+            if cmap is not None:
+                ops._require_device(cmap, "the shader's lookup table")
+                cmap = cmap.detach()
         flags = ops.default_flags(loop.early_out, loop.tile8x8, loop.dynamic_tiles, loop.regen is True, loop.order_per_ray)
         cs, table, params = self.cs, self.table, self.params
 
@@ -420,18 +435,21 @@ class RenderLoop(nn.Module):
         scheduling hint and per-tile cost output (include/rm_abi.h).  ``mode``: one of the reference's eight shaders, or an
         instance of a class registered with extensions.register_shader ([N, H, W, 3] in the module's dtype; its own
         parameters receive gradients like the scene's)."""
+        shader = mode
         mode, cs = resolve_mode(self.scene, mode, self.precision)
+        table = _shader_table(cs, shader) if mode == _abi.MODE_USER else None
         r0 = self.camera.rows[0]
         if rows is not None and r0:          # a band loop: frame rows -> rows of its own buffers
             if rows[0] < r0 or rows[1] > self.camera.rows[1]:
                 raise ValueError(f"rows {tuple(rows)} outside this loop's band {self.camera.rows}")
             rows = (rows[0] - r0, rows[1] - r0)
         training = torch.is_grad_enabled() and (orientations.requires_grad or translations.requires_grad
-                                                or any(p.requires_grad for p in cs.leaves))
+                                                or any(p.requires_grad for p in cs.leaves)
+                                                or (table is not None and table.requires_grad))
         rp, rd = self._io_buffers(training)
         ops._require_device(rp, "camera buffers")          # no CPU path: fail here, with the reason, not in a stream query
         ops._require_device(orientations, "orientations")
-        cmap = self._cmap(rp.device) if mode in (6, 7) else None
+        cmap = self._cmap(rp.device) if mode in (6, 7) else table      # (a user shader's lookup table travels in the colormap slot)
         # The kernels gather the parameter block from the nn.Parameter storages themselves (nothing to pack,
         # nothing to go stale); a training frame hands the Parameters to the autograd Function as its leaves.
         # Only parameters that cannot be read in place (other device / dtype) are packed with torch.cat.

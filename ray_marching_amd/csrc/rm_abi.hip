@@ -207,6 +207,23 @@ int rm_user_shaders(void) {
 #endif
 }
 
+int rm_user_shader_table(void) {
+#ifdef RM_USER_SHADER_TABLE
+  return RM_USER_SHADER_TABLE_TAPS;
+#else
+  return 0;
+#endif
+}
+
+// RM_MODE_USER of a library whose shader reads a lookup table: the table in the colormap slot (float32 [2..RM_TABLE_MAX_ROWS, 3])
+static bool user_table_ok([[maybe_unused]] int mode, [[maybe_unused]] const void* cmap, [[maybe_unused]] int cmap_size,
+                          [[maybe_unused]] int cmap_dtype) {
+#ifdef RM_USER_SHADER_TABLE
+  if (mode == RM_MODE_USER) return cmap && cmap_dtype == RM_DTYPE_F32 && cmap_size >= 2 && cmap_size <= RM_TABLE_MAX_ROWS;
+#endif
+  return true;
+}
+
 const char* rm_last_error(void) { return g_err; }
 
 int64_t rm_grad_partials_floats(const RmScene* scene, int64_t n) {
@@ -376,6 +393,9 @@ int rm_render_forward(const RmScene* scene, const RmCamera* cam, const RmTetra* 
     return fail(RM_E_BADARG, "rm_render_forward: mode %d needs a minmax workspace and a first_pass buffer", mode);
   if (mapped && (!cmap || cmap_size <= 0 || cmap_dtype < RM_DTYPE_F32 || cmap_dtype > RM_DTYPE_F64))
     return fail(RM_E_BADARG, "rm_render_forward: mode %d needs a colormap (F32, F16 or F64)", mode);
+  if (!user_table_ok(mode, cmap, cmap_size, cmap_dtype))
+    return fail(RM_E_BADARG, "rm_render_forward: this library's user shader needs its lookup table (float32 [2..%d, 3]) in the colormap slot",
+                RM_TABLE_MAX_ROWS);
   if (!(io_dtype_ok(image_dtype) || (image_dtype == RM_DTYPE_F64 && mapped) || (image_dtype == RM_DTYPE_RGBA_F32 && cam->num_cameras == 1)))
     return fail(RM_E_BADARG, "rm_render_forward: image dtype %d (F64 only for modes 6, 7; RGBA_F32 only for one camera)", image_dtype);
   if (image_dtype == RM_DTYPE_RGBA_F32 && (reinterpret_cast<uintptr_t>(image) & 15))
@@ -648,6 +668,18 @@ int rm_render_backward(const RmScene* scene, const RmCamera* cam, const RmTetra*
                        int32_t cmap_dtype, int32_t mode, int32_t degree,
                        int32_t steps, int32_t row_begin, int32_t row_end, int32_t flags, int32_t* tile_cost,
                        float* hard_ws, int64_t hard_capacity, void* stream) {
+  return rm_render_backward_table(scene, cam, tetra, orientation, translation, traj, nexec, p_final, normal_u, grad_image, grad_params,
+                                  partials, work, grad_pos, grad_dirs, grad_qdir, cmap, cmap_size, cmap_dtype, mode, degree, steps,
+                                  row_begin, row_end, flags, tile_cost, hard_ws, hard_capacity, nullptr, stream);
+}
+
+int rm_render_backward_table(const RmScene* scene, const RmCamera* cam, const RmTetra* tetra, const float* orientation,
+                             const float* translation, const float* traj, const int32_t* nexec, const float* p_final,
+                             const float* normal_u, const float* grad_image, float* grad_params, float* partials, uint32_t* work,
+                             float* grad_pos, float* grad_dirs, float* grad_qdir, const void* cmap, int32_t cmap_size,
+                             int32_t cmap_dtype, int32_t mode, int32_t degree,
+                             int32_t steps, int32_t row_begin, int32_t row_end, int32_t flags, int32_t* tile_cost,
+                             float* hard_ws, int64_t hard_capacity, float* table_records, void* stream) {
 #ifdef RM_NO_BACKWARD
   return fail(RM_E_BADARG, "rm_render_backward: this specialised library was built forward-only");
 #else
@@ -658,6 +690,12 @@ int rm_render_backward(const RmScene* scene, const RmCamera* cam, const RmTetra*
   if (mapped && (!cmap || cmap_size <= 0 || cmap_dtype < RM_DTYPE_F32 || cmap_dtype > RM_DTYPE_F64))
     return fail(RM_E_BADARG, "rm_render_backward: mode %d needs the colormap of the forward call", mode);
   if (!p_final || !grad_image || !partials || (steps > 0 && !traj)) return fail(RM_E_BADARG, "rm_render_backward: null buffer");
+  if (!user_table_ok(mode, cmap, cmap_size, cmap_dtype))
+    return fail(RM_E_BADARG, "rm_render_backward: this library's user shader needs the lookup table of the forward call (float32 [2..%d, 3])",
+                RM_TABLE_MAX_ROWS);
+  if (table_records && (rm_user_shader_table() == 0 || mode != RM_MODE_USER || (reinterpret_cast<uintptr_t>(table_records) & 15)))
+    return fail(RM_E_BADARG, "rm_render_backward_table: table_records (16-byte aligned) are written by RM_MODE_USER of a library whose user "
+                             "shader reads a lookup table");
   rm::RenderArgs a;
   memset(&a, 0, sizeof(a));
   a.scene = *scene; a.cam = *cam; a.tetra = *tetra;
@@ -667,6 +705,7 @@ int rm_render_backward(const RmScene* scene, const RmCamera* cam, const RmTetra*
   a.grad_image = grad_image; a.partials = partials; a.minmax = work;
   a.grad_pos = grad_pos; a.grad_dirs = grad_dirs; a.grad_qdir = grad_qdir; a.tile_cost = tile_cost;
   a.cmap = cmap; a.cmap_size = cmap_size; a.cmap_dtype = cmap_dtype; a.degree = degree;
+  a.table_records = table_records;
   a.mode = mode; a.steps = steps; a.row_begin = row_begin; a.row_end = row_end; a.flags = flags & (RM_FLAG_TILE8X8 | RM_FLAG_DYNAMIC_TILES | RM_FLAG_EARLY_OUT);
   const RenderKernel kernel = render_bwd_kernel(mode);
   Launch L;
@@ -757,6 +796,26 @@ int rm_tile_score_from_ray_cost(const int32_t* ray_cost, int64_t n_tiles, int32_
   rm::k_tile_score_classes<<<grid_for((n_tiles + 255) / 256, kMaxBlocks), 256, 0, (hipStream_t)stream>>>(
       raw, n_tiles, tiles_x, tiles_y, reach, max_cost, tile_score);
   return launched("k_tile_score_classes");
+}
+
+int rm_table_scatter(const float* records, int64_t n_records, int32_t table_rows, float* grad_table, float* partials, void* stream) {
+  if (table_rows < 2 || table_rows > RM_TABLE_MAX_ROWS || n_records < 0 || !grad_table || (n_records > 0 && (!records || !partials)) ||
+      (reinterpret_cast<uintptr_t>(records) & 15))
+    return fail(RM_E_BADARG, "rm_table_scatter: bad args (2 <= table_rows <= %d, records 16-byte aligned)", RM_TABLE_MAX_ROWS);
+  const int width = 3 * table_rows;
+  if (n_records == 0) {
+    if (hipMemsetAsync(grad_table, 0, sizeof(float) * width, (hipStream_t)stream) != hipSuccess)
+      return fail(RM_E_LAUNCH, "rm_table_scatter: clearing grad_table failed");
+    return RM_OK;
+  }
+  const int64_t chunks = (n_records + RM_TABLE_CHUNK - 1) / RM_TABLE_CHUNK;
+  if (chunks > 0x7fffffff) return fail(RM_E_BADARG, "rm_table_scatter: too many records");
+  // one wave per chunk, its private table in LDS: 12 L bytes, 48 KB at the longest table (below the 64 KB no attribute is needed for)
+  rm::k_table_scatter<<<(int)chunks, 64, sizeof(float) * width, (hipStream_t)stream>>>(reinterpret_cast<const float4*>(records), n_records,
+                                                                                        table_rows, partials);
+  if (int e = launched("k_table_scatter")) return e;
+  rm::k_reduce_partials<<<width, 256, 0, (hipStream_t)stream>>>(partials, (int)chunks, width, grad_table);
+  return launched("k_reduce_partials");
 }
 
 int rm_sum_rows(const float* rows, int64_t n_rows, int32_t width, float* out, void* stream) {

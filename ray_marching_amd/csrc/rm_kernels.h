@@ -743,6 +743,8 @@ struct RenderArgs {
   float* hard_p;             // [steps][cap][4] the iterate p_s itself (k_bwd_hard_b reads it by pair code: no ray -> nexec -> trajectory chain)
   uint32_t* hard_pairs;      // [steps * cap] (ray slot << 11 | step) of every pair with g != 0, densely packed
   int32_t hard_cap;
+  // backward of a user shader with a lookup table (RM_USER_SHADER_TABLE), nullable: [R][T][4] records (row, dL/d(row)) for k_table_scatter
+  float* table_records;
 };
 
 #define RM_WORK_HARD_COUNT 32      // workspace word (own 128-B line): rays deferred by k_render_bwd
@@ -942,6 +944,21 @@ struct ShadeGrad {
   float qw; V3 qv;
 };
 
+// The lookup table of a user shader (register_shader(table=..., table_taps=T)): [n,3] float32 in global memory, the colormap slot
+// of the frame ABI.  row() clamps the index: whatever a shader computes, it reads a row of the table.
+struct Table {
+  const float* rows;
+  int n;
+  RM_DEV int clamp(int i) const { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
+  RM_DEV V3 row(int i) const { return load3(rows, clamp(i)); }
+};
+// dL/d(table) of one pixel as the shader's VJP fills it in: up to T (row, gradient) pairs, indexed by constants only; row -1: unused
+#define RM_USER_SHADER_MAX_TABLE_TAPS 4
+struct TableGrad {
+  int row[RM_USER_SHADER_MAX_TABLE_TAPS] = {-1, -1, -1, -1};
+  V3 g[RM_USER_SHADER_MAX_TABLE_TAPS] = {};
+};
+
 // User-defined per-pixel shader (RM_MODE_USER; extensions.register_shader).  The code header of a specialised library is
 // included a third time here, behind ShadeIn / ShadeGrad and still inside namespace rm, for its shader section alone
 // (RM_STATIC_CODE_LEAVES keeps the program section of a header without one out):
@@ -1051,7 +1068,11 @@ struct UserShader {
   RM_DEV V3 fwd(const ShadeIn& si) const { return user_shader_fwd<false>(si, theta.v, d); }
 #else
   template <class SceneT> RM_DEV void probe(const SceneT&, const ShadeIn&) {}
-#ifdef RM_USER_SHADER
+#ifdef RM_USER_SHADER_TABLE
+  // a shader with a lookup table (register_shader(table=...)): the frame's colormap slot, set by RM_USER_TABLE_SET in front of fwd
+  Table tab{nullptr, 0};
+  RM_DEV V3 fwd(const ShadeIn& si) const { return user_shader_fwd<false>(si, theta.v, tab); }
+#elif defined(RM_USER_SHADER)
   RM_DEV V3 fwd(const ShadeIn& si) const { return user_shader_fwd<false>(si, theta.v); }
 #endif
 #endif
@@ -1070,6 +1091,12 @@ struct UserShader {
 #define RM_OR_USER_NORMALISED(mode) || (mode) == RM_MODE_USER
 #else
 #define RM_OR_USER_NORMALISED(mode)
+#endif
+// ... and the table of a shader that has one is handed over as text too: nothing in every other library
+#ifdef RM_USER_SHADER_TABLE
+#define RM_USER_TABLE_SET(us, a) (us).tab = Table{static_cast<const float*>((a).cmap), (a).cmap_size};
+#else
+#define RM_USER_TABLE_SET(us, a)
 #endif
 
 // third column of the camera rotation (QuaternionToSO3, quaternion.py:114-124): pixel_frames[..., 2]
@@ -1381,6 +1408,7 @@ RM_DEV void finish_tile(const RenderArgs& a, const SceneT& scene, const Tetra& T
   si.qw = r.ps.w; si.qv = r.ps.qv; si.col2 = col2_of(r.ps);
   if (UserShader::kEnabled && mode == RM_MODE_USER) si.lap = 0.0f;       // (the taps' sum without the centre value is no Laplacian: a user shader reads 0)
   UserShader us(scene.P);
+  RM_USER_TABLE_SET(us, a)
   if (UserShader::kEnabled && mode == RM_MODE_USER) us.probe(scene, si);   // (mode is uniform: every lane of the wave evaluates)
   const Shaded sh = shade_pixel(mode, si, a.cmap_size, a.degree, &us);
   const V3 out = sh.rgb;
@@ -2357,6 +2385,22 @@ __global__ void __launch_bounds__(256) RM_BWD_OCC k_render_bwd(RenderArgs a) {
         user_shader_probe_vjp<(RM_FAST_VJP != 0)>(k, si, theta, gq, gs, gtheta);
       }
 #endif
+#elif defined(RM_USER_SHADER_TABLE)
+      // a shader with a lookup table: its VJP also hands back up to T (row, dL/d(row)) pairs.  Where the table wants a gradient
+      // (a.table_records: a run-time choice, the library is the same) the pixel's T records go out as one float4 each, at the
+      // pixel's own index -- every pixel of the band belongs to exactly one live lane, so lanes without a pixel store nothing --
+      // with the row clamped (or -1: no contribution); k_table_scatter sums them in an order that depends on that index alone.
+      const Table tab{static_cast<const float*>(a.cmap), a.cmap_size};
+      TableGrad gt;
+      user_shader_vjp<(RM_FAST_VJP != 0)>(si, theta, tab, gi3, gs, gtheta, gt);
+      if (a.table_records && live) {
+#pragma unroll
+        for (int k = 0; k < RM_USER_SHADER_TABLE_TAPS; ++k) {
+          const int r = gt.row[k] < 0 ? -1 : tab.clamp(gt.row[k]);
+          *reinterpret_cast<float4*>(a.table_records + 4 * ((int64_t)li * RM_USER_SHADER_TABLE_TAPS + k)) =
+              make_float4(__int_as_float(r), gt.g[k].x, gt.g[k].y, gt.g[k].z);
+        }
+      }
 #else
       user_shader_vjp<(RM_FAST_VJP != 0)>(si, theta, gi3, gs, gtheta);
 #endif
@@ -2620,6 +2664,58 @@ __global__ void k_reduce_partials(const float* __restrict__ partials, int nblock
     __syncthreads();
   }
   if (threadIdx.x == 0) sums[i] = red[0];
+}
+
+// Gradient of a user shader's lookup table: the scatter-add of the (row, dL/d(row)) records the fused backward left, one per
+// pixel and tap, into [L,3] -- without float atomics and in an order that depends on nothing but the record index.
+// One wave (one block of 64 threads) owns the records [chunk * RM_TABLE_CHUNK, (chunk + 1) * RM_TABLE_CHUNK) -- a constant of
+// the ABI, not of the grid -- and a private 3 L-float table in LDS (48 KB at L = 4096).  It walks its chunk 64 records at a
+// time, in order; of each 64 it peels the distinct rows, lowest holding lane first: the lanes that hold the row are summed by the
+// fixed DPP ladder of the accumulator rows (wave_sum_lane63; the other lanes add exact zeros), and lane 63 -- the only lane that
+// ever touches the LDS table between the two barriers -- does the read-modify-write.  A row held by one lane alone skips the
+// ladder (the sum of one value and 63 zeros is that value: the same bits).  The per-chunk tables go to partials[chunk][3 L];
+// k_reduce_partials, the fixed tree every other gradient ends in, makes the result.  Rows outside [0, L) contribute nothing.
+__global__ void __launch_bounds__(64) k_table_scatter(const float4* __restrict__ records, int64_t n_records, int L,
+                                                      float* __restrict__ partials) {
+  float* tab = rm_smem;
+  const int lane = threadIdx.x;
+  for (int i = lane; i < 3 * L; i += 64) tab[i] = 0.0f;
+  __syncthreads();
+  const int64_t begin = (int64_t)blockIdx.x * RM_TABLE_CHUNK;
+  for (int j = 0; j < RM_TABLE_CHUNK; j += 64) {
+    const int64_t at = begin + j + lane;
+    if (begin + j >= n_records) break;           // (uniform: the last chunk is partial)
+    int row = -1;
+    V3 g = mk3(0.0f, 0.0f, 0.0f);
+    if (at < n_records) {
+      const float4 r = records[at];
+      row = __float_as_int(r.x);
+      g = mk3(r.y, r.z, r.w);
+    }
+    if (row >= L) row = -1;
+    unsigned long long pending = __ballot(row >= 0);
+    while (pending) {                            // (uniform: every lane walks every distinct row)
+      const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)pending) - 1);
+      const int r = __builtin_amdgcn_readlane(row, leader);
+      const bool mine = row == r;
+      const unsigned long long m = __ballot(mine);
+      float sx, sy, sz;
+      if (__popcll(m) == 1) {
+        sx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, g.x), leader));
+        sy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, g.y), leader));
+        sz = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, g.z), leader));
+      } else {
+        sx = wave_sum_lane63(mine ? g.x : 0.0f);
+        sy = wave_sum_lane63(mine ? g.y : 0.0f);
+        sz = wave_sum_lane63(mine ? g.z : 0.0f);
+      }
+      if (lane == 63) { tab[3 * r] += sx; tab[3 * r + 1] += sy; tab[3 * r + 2] += sz; }
+      pending &= ~m;
+    }
+  }
+  __syncthreads();
+  float* out = partials + (int64_t)blockIdx.x * (3 * L);
+  for (int i = lane; i < 3 * L; i += 64) out[i] = tab[i];
 }
 
 // Stage 2: push the gradients of the derived capsule constants back onto start/end

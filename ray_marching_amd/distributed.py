@@ -187,7 +187,9 @@ class RowTileRenderer:
 
 def all_reduce_gradients(module: torch.nn.Module, group=None):
     """Sum the scene-parameter gradients over the ranks (each rank back-propagated the loss of
-    its own band).  One flat P-float all-reduce."""
+    its own band).  One flat P-float all-reduce.  Called with a user shader it sums that shader's ``theta`` and, where its
+    lookup table is a Parameter (``register_shader(table=...)``), the table's ``[L, 3]`` gradient with it: every rank scattered the
+    records of its own band."""
     if not dist.is_initialized() or dist.get_world_size(group) == 1:
         return
     params = [p for p in module.parameters() if p.requires_grad]

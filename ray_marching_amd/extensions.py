@@ -139,6 +139,26 @@ pixel with ``raw.x == lo`` and ``sum ghi / n_hi`` to every pixel with ``raw.x ==
 NotImplementedError, as for the built-in distance, proximity and Laplacian modes; a frame with ``lo == hi`` is whatever
 ``NAME_finish`` makes of it.
 
+*Lookup tables* give a shader storage it may index at run time (``theta`` lives in registers and is indexed by constants only): a
+palette, a transfer function, a learnable 1-D texture.  ``register_shader(..., table="ATTR", table_taps=T)`` names an attribute of
+the instance -- a registered buffer or an ``nn.Parameter`` (NOT listed in ``params``), float32, contiguous, ``[L, 3]`` with ``2 <= L <=
+4096`` -- and the most rows ``T`` (1 to 4) one pixel's VJP contributes to (1: a nearest lookup, 2: a linear interpolation).  The pair
+becomes
+
+    template <bool Fast> RM_DEV rm::V3 NAME_fwd(const rm::ShadeIn& s, const float* theta, const rm::Table& tab);
+    template <bool Fast> RM_DEV void   NAME_vjp(const rm::ShadeIn& s, const float* theta, const rm::Table& tab, rm::V3 g,
+                                                rm::ShadeGrad& gs, float* gtheta, rm::TableGrad& gt);
+
+``tab.n`` is ``L`` (a run-time value, like the table's contents: one library serves every length) and ``tab.row(i)`` is row ``i`` as a
+``V3``, read from global memory, with ``i`` clamped to ``[0, L-1]`` inside ``row``: a wild index reads a valid row and never faults (an
+index made from a NaN is the author's business).  ``gt.row[k]`` / ``gt.g[k]`` arrive as ``-1`` / zero for ``k < T``; the VJP writes ``gt.row[k] =
+i; gt.g[k] = dL/d(row i)`` (``i`` as ``tab.row`` clamps it: ``tab.clamp(i)``), indexes them with constants only like ``gtheta``, and
+leaves at ``-1`` what it does not use.  Where the table is a Parameter that requires grad, the fused backward stores the ``T`` records
+of every pixel and a second kernel sums them into the ``[L, 3]`` gradient without float atomics, in an order that depends only on
+the pixel's index: two backwards give the same bits.  A buffer table (or ``requires_grad=False``) stores nothing.  The PyTorch
+``forward`` needs nothing new: it indexes ``self.ATTR``.  ``table=`` together with ``probes`` or ``normalise=`` is refused at registration
+(not built yet).
+
 Scenes that contain such a leaf, combinator or warp, and frames shaded by such a shader, run only through their per-scene specialised library (specialize.py), into which
 the source is compiled; the LDS interpreter has no handler for them and ``CompiledScene.lib()`` says so instead of
 rendering a wrong picture.
@@ -199,6 +219,8 @@ class UserShader(_UserSpec):
     probes: int = 0     # K: the scene evaluations the shader asks for per pixel (NAME_probe / NAME_probe_vjp); 0: none
     chained: bool = False   # probe k may depend on the values of the probes before it (the pair takes the history h / gh)
     normalise: object = None    # "minmax": NAME_fwd returns the raw triple, NAME_finish / NAME_finish_vjp map it through the frame's min / max
+    table: str = ""     # attribute that holds the lookup table ([L, 3] float32 buffer or nn.Parameter; the pair takes tab / gt); "": none
+    table_taps: int = 0     # T: the most table rows one pixel's VJP contributes to (1..RM_USER_SHADER_MAX_TABLE_TAPS); 0: no table
 
 
 @dataclass(frozen=True)
@@ -245,10 +267,12 @@ _KINDS = {
         "`template <bool Fast> RM_DEV void NAME_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 g, rm::ShadeGrad& gs, float* "
         "gtheta)`",
         methods=(("forward", "forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals)"),),
-        same=("sha1", "params", "probes", "chained", "normalise"), device_forward=False, probe_pair=True, finish_pair=True),
+        same=("sha1", "params", "probes", "chained", "normalise", "table", "table_taps"), device_forward=False, probe_pair=True, finish_pair=True),
 }
 
 NORMALISATIONS = (None, "minmax")    # register_shader(normalise=...): the frame statistics a shader may be normalised by
+RM_USER_SHADER_MAX_TABLE_TAPS = 4   # the most table rows one pixel's VJP may contribute to (gt.row[] / gt.g[] live in registers)
+RM_USER_SHADER_MAX_TABLE_ROWS = 4096    # the longest lookup table (the size of the reference's own colormap: 48 KB of float32)
 RM_USER_SHADER_MAX_PROBES = 8       # the most scene probes a shader may ask for (d[] / gd[] live in registers: INTEGRATION.md)
 
 _registry: dict[type, _UserSpec] = {}       # registered class -> its registration, of whichever kind
@@ -297,6 +321,18 @@ def _parse(kind: str, hip: str):
                          f"rm::V3& graw, float& glo, float& ghi, float* gtheta)`: both or neither (found {name}_finish: {finish_fwd}, "
                          f"{name}_finish_vjp: {finish_vjp})")
     return name, out_fwd, bool(row.bound) and _has_bound(text, name, row.bound), probe_fwd, finish_fwd
+
+
+def _table_arguments(hip: str, name: str):
+    """(NAME_fwd takes a ``rm::Table``, NAME_vjp takes a ``rm::TableGrad``): read from the two parameter lists of the source."""
+    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
+
+    def arguments(fn):
+        m = re.search(r"\b%s_%s\s*\(([^)]*)\)" % (re.escape(name), fn), text)
+        return m.group(1) if m else ""
+
+    return (re.search(r"\bTable\s*&", arguments("fwd")) is not None and re.search(r"\bTable\s*&", arguments("vjp")) is not None,
+            re.search(r"\bTableGrad\s*&", arguments("vjp")) is not None)
 
 
 def _has_bound(text: str, name: str, what: str) -> bool:
@@ -394,6 +430,28 @@ def _register(kind: str, cls, *, params, hip: str, **own):
             raise ValueError(f"{fn}: the source of {cls.__name__} defines {name}_finish / {name}_finish_vjp, but normalise=None")
         if normalise is not None and not has_finish:
             raise ValueError(f"{fn}: normalise={normalise!r}, but the source of {cls.__name__} defines no {name}_finish / {name}_finish_vjp")
+    if "table" in own:
+        table, taps = own["table"], own["table_taps"]
+        if not isinstance(table, str):
+            raise ValueError(f"{fn}: table must name the attribute that holds the lookup table, not {table!r}")
+        if isinstance(taps, bool) or not isinstance(taps, int) or not 0 <= taps <= RM_USER_SHADER_MAX_TABLE_TAPS or (table and taps == 0):
+            raise ValueError(f"{fn}: table_taps must be an int from 1 to RM_USER_SHADER_MAX_TABLE_TAPS = {RM_USER_SHADER_MAX_TABLE_TAPS} "
+                             f"(the most rows one pixel's VJP contributes to), not {taps!r}")
+        if taps and not table:
+            raise ValueError(f"{fn}: table_taps={taps} without table= (the attribute that holds the lookup table)")
+        if table and (own["probes"] > 0 or own["normalise"] is not None):
+            raise ValueError(f"{fn}: table= together with probes > 0 or normalise= is not built yet (DESIGN.md section 11): a shader reads "
+                             f"a lookup table or probes the scene / is normalised by the frame, not both")
+        if table in params:
+            raise ValueError(f"{fn}: the table attribute {table!r} must not be listed in params (it is no part of theta)")
+        has_tab, has_gt = _table_arguments(hip, name)
+        if table and not (has_tab and has_gt):
+            raise ValueError(f"{fn}: table={table!r}, but the source of {cls.__name__} does not define `template <bool Fast> RM_DEV rm::V3 "
+                             f"{name}_fwd(const rm::ShadeIn& s, const float* theta, const rm::Table& tab)` and `template <bool Fast> RM_DEV "
+                             f"void {name}_vjp(const rm::ShadeIn& s, const float* theta, const rm::Table& tab, rm::V3 g, rm::ShadeGrad& gs, "
+                             f"float* gtheta, rm::TableGrad& gt)` (found tab: {has_tab}, gt: {has_gt})")
+        if not table and (has_tab or has_gt):
+            raise ValueError(f"{fn}: the source of {cls.__name__} takes a rm::Table / rm::TableGrad, but no table= was given")
     if row.out_pair and has_out != callable(getattr(cls, "out", None)):
         raise TypeError(f"{fn}: {cls.__name__} " + (
             f"has no out(values, points) method, but its source defines {name}_out_fwd / {name}_out_vjp" if has_out else
@@ -414,7 +472,9 @@ def _register(kind: str, cls, *, params, hip: str, **own):
                              + (" (or another number of probes)" if row.probe_pair and old.probes != spec.probes else "")
                              + (f" (chained={old.chained} before, chained={spec.chained} now)" if row.probe_pair and old.chained != spec.chained else "")
                              + (f" (normalise={old.normalise!r} before, normalise={spec.normalise!r} now)"
-                                if row.finish_pair and old.normalise != spec.normalise else ""))
+                                if row.finish_pair and old.normalise != spec.normalise else "")
+                             + (f" (table={old.table!r}, table_taps={old.table_taps} before, table={spec.table!r}, table_taps={spec.table_taps} now)"
+                                if "table" in own and (old.table, old.table_taps) != (spec.table, spec.table_taps) else ""))
         return cls
     for other in _registry.values():
         if other.name == spec.name:          # (a scene's user types and the shader are compiled into one translation unit)
@@ -510,7 +570,8 @@ def warp_child(node, spec: UserWarp):
     return kid
 
 
-def register_shader(cls, *, params=(), hip: str, probes: int = 0, chained: bool = False, normalise=None):
+def register_shader(cls, *, params=(), hip: str, probes: int = 0, chained: bool = False, normalise=None, table: str = "",
+                    table_taps: int = 0):
     """Make instances of ``cls`` (an ``nn.Module`` subclass) usable as the ``mode`` of ``RenderLoop.forward``: a per-pixel shader
     that runs fused at the end of the frame kernels and in the fused backward.
 
@@ -527,12 +588,18 @@ def register_shader(cls, *, params=(), hip: str, probes: int = 0, chained: bool 
     normalise: None (the default: ``NAME_fwd`` returns the pixel's colour), or "minmax": ``NAME_fwd`` returns the pixel's raw triple, the
             frame takes ``lo = min raw.x`` / ``hi = max raw.x`` over all pixels of all cameras, and the source brings NAME_finish /
             NAME_finish_vjp, which make the colour of ``(raw, lo, hi, theta)`` (module docstring: "frame-normalised shaders").
+    table:  the attribute of the INSTANCE that holds a lookup table: a registered buffer or an ``nn.Parameter``, float32, contiguous,
+            ``[L, 3]`` with ``2 <= L <= 4096``.  NAME_fwd / NAME_vjp then take ``const rm::Table& tab`` behind theta and the VJP ``rm::TableGrad&
+            gt`` at its end (module docstring: "lookup tables").  A Parameter table is NOT listed in ``params``; it receives its ``.grad``
+            through a deterministic scatter.  Not together with ``probes`` or ``normalise`` (not built yet).
+    table_taps: T, 1 to 4: the most table rows one pixel's VJP contributes to (1: a nearest lookup, 2: a linear interpolation).
 
     ``cls`` has ``forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals) -> [..., 3]``,
     the first six arguments of the reference's ``Shader.forward`` (``camera_orientation`` [N,4], ``pixel_frames`` [N,3,3]); it is
     the CPU statement of the shader and is NOT replaced.  Registering a class again with the same source is a no-op; with other
-    source, parameters, number of probes or value of ``chained`` / ``normalise`` it is an error.  Identifiers are unique across all four kinds (leaves, combinators, warps and shaders)."""
-    return _register("shader", cls, params=params, hip=hip, probes=probes, chained=chained, normalise=normalise)
+    source, parameters, number of probes or value of ``chained`` / ``normalise`` / ``table`` / ``table_taps`` it is an error.  Identifiers are unique across all four kinds (leaves, combinators, warps and shaders)."""
+    return _register("shader", cls, params=params, hip=hip, probes=probes, chained=chained, normalise=normalise, table=table,
+                     table_taps=table_taps)
 
 
 def shader_spec(node):
@@ -544,11 +611,30 @@ def shader_parameters(shader, spec: UserShader):
     """The shader's nn.Parameters in theta order: the registered names, which must be all of its parameters in
     ``named_parameters()`` order."""
     params = leaf_parameters(shader, spec)
-    own = [p for _, p in shader.named_parameters()]
+    table = getattr(shader, spec.table, None) if spec.table else None      # (a Parameter table is no part of theta)
+    own = [p for _, p in shader.named_parameters() if p is not table]
     if len(own) != len(params) or any(a is not b for a, b in zip(own, params)):
         raise ValueError(f"{type(shader).__name__}: the registered params {spec.params} are not all of the shader's parameters in "
                          f"named_parameters() order ({[n for n, _ in shader.named_parameters()]})")
     return params
+
+
+def shader_table(shader, spec: UserShader):
+    """The lookup table of a shader instance registered with ``table=``: the tensor the kernels read in place (a buffer or an
+    ``nn.Parameter``; float32, contiguous, ``[L, 3]``, ``2 <= L <= RM_USER_SHADER_MAX_TABLE_ROWS``), or None for a shader without one."""
+    if not spec.table:
+        return None
+    t = getattr(shader, spec.table, None)
+    what = f"{type(shader).__name__}.{spec.table}"
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: the registered table attribute is missing or no tensor")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what}: a lookup table is float32, not {t.dtype}")
+    if t.dim() != 2 or t.shape[1] != 3 or not 2 <= t.shape[0] <= RM_USER_SHADER_MAX_TABLE_ROWS:
+        raise ValueError(f"{what}: a lookup table is [L, 3] with 2 <= L <= {RM_USER_SHADER_MAX_TABLE_ROWS}, not {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: a lookup table must be contiguous (the kernels read it in place)")
+    return t
 
 
 def leaf_parameters(node, spec):

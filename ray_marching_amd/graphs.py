@@ -88,7 +88,7 @@ class CapturedTrainingStep:
         self.q = orientations.detach().clone().requires_grad_(self.pose_requires_grad)
         self.t = translations.detach().clone().requires_grad_(self.pose_requires_grad)
         self.params = [p for p in loop.scene.parameters() if p.requires_grad]
-        if isinstance(self.mode, torch.nn.Module):       # a user shader's own parameters are trained with the scene's
+        if isinstance(self.mode, torch.nn.Module):       # a user shader's own parameters (a Parameter lookup table too) are trained with the scene's
             self.params += [p for p in self.mode.parameters() if p.requires_grad]
         leaves = self.params + ([self.q, self.t] if self.pose_requires_grad else [])
 

@@ -459,6 +459,13 @@ def laplacian_normalisation_vjp(grad_image: torch.Tensor, lap: torch.Tensor, hi:
     return glap + torch.where(top, (ghi / top.sum()) * lap.sign(), torch.zeros_like(glap))
 
 _N_FIXED_ARGS = 18                   # Render.forward arguments in front of *leaves
+_CMAP_ARG = 7                        # ... of which this one is the colormap -- or the lookup table of a user shader, which may want a gradient
+
+
+def user_table(cs, mode) -> bool:
+    """Whether ``mode`` on the program ``cs`` is a user shader that reads a lookup table (register_shader(table=...)): the table then
+    travels in the colormap slot, and a table that requires grad gets its gradient from the records of the fused backward."""
+    return mode == _abi.MODE_USER and bool(cs.user_shader_table)
 
 
 # measurement hook (bench.py): when set to a list, Render.run appends a (start, end) pair of timing events
@@ -469,6 +476,25 @@ kernel_event_sink = None
 park_rays = os.environ.get("RM_PARK", "0") == "1"
 bwd_hard_capacity = None      # None: default sizing of the deferred-ray list of rm_render_backward; 0 = off (A/B probes)
 bwd_tile_cost_sink = None     # measurement hook (profiles/): int32 [wave tiles] tensor receiving rm_render_backward's tile_cost
+
+
+table_scatter_calls = 0      # how many times table_scatter ran (tests: a table that wants no gradient launches none)
+
+
+def table_scatter(records: torch.Tensor, table_rows: int, stream=None) -> torch.Tensor:
+    """[L, 3] gradient of a lookup table from the ``[R, T, 4]`` records of rm_render_backward_table (row as int32 bits, dL/d(row)):
+    rm_table_scatter, deterministic -- no float atomics, every sum in an order fixed by the record index."""
+    global table_scatter_calls
+    table_scatter_calls += 1
+    dev = records.device
+    n = records.numel() // 4
+    chunks = (n + _abi.TABLE_CHUNK - 1) // _abi.TABLE_CHUNK
+    out = torch.empty((table_rows, 3), dtype=torch.float32, device=dev)
+    part = torch.empty(max(chunks, 1) * 3 * table_rows, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(_lib.rm_table_scatter(_abi.ptr(records), n, table_rows, _abi.ptr(out), _abi.ptr(part),
+                                         stream if stream is not None else _abi.current_stream(dev)), "rm_table_scatter")
+    return out
 
 
 class Render(torch.autograd.Function):
@@ -503,7 +529,12 @@ class Render(torch.autograd.Function):
         _require_device(orientation, "orientations")
         dev = ray_positions.device
         prm = None if params is None else _f32c(params)       # None: the kernel gathers from the parameter storages
-        need_grad = any(needs_input_grad[:3]) or any(needs_input_grad[_N_FIXED_ARGS:])
+        table_grad = user_table(cs, mode) and len(needs_input_grad) > _CMAP_ARG and bool(needs_input_grad[_CMAP_ARG])
+        need_grad = any(needs_input_grad[:3]) or any(needs_input_grad[_N_FIXED_ARGS:]) or table_grad
+        if user_table(cs, mode):
+            if cmap is None or cmap.dtype != torch.float32 or cmap.dim() != 2 or cmap.shape[1] != 3 or not cmap.is_contiguous():
+                raise ValueError("a user shader with a lookup table renders with that table (float32, contiguous, [L, 3])")
+            _require_device(cmap, "the shader's lookup table")
         have_vjp = mode in _FUSED_VJP_MODES
         record = need_grad and have_vjp
         if record and (ray_positions.dtype != torch.float32 or ray_directions.dtype != torch.float32):
@@ -600,7 +631,9 @@ class Render(torch.autograd.Function):
         if record:
             # the leaves are saved too: autograd then refuses a backward after an in-place edit of a parameter
             # (the backward kernels read the live storages, which must still hold the forward's values)
-            ctx.save_for_backward(prm, q, t, rp, rd, p_final, traj, nexec, normal_u, *leaves)
+            # (... and so is a user shader's lookup table, behind them)
+            ctx.table_saved = user_table(cs, mode)
+            ctx.save_for_backward(prm, q, t, rp, rd, p_final, traj, nexec, normal_u, *leaves, *((cmap,) if ctx.table_saved else ()))
             # Laplacian shader: the un-normalised values and their largest magnitude, for the normalisation's VJP
             ctx.lap = (first_pass, lohi, allreduce_minmax is not None) if (mode in _GLOBAL_MODES or user_norm) else None
             ctx.user_norm = user_norm
@@ -616,6 +649,7 @@ class Render(torch.autograd.Function):
             # only differentiating through a shader without a fused VJP is refused
             raise NotImplementedError(f"fused backward exists for shader modes {sorted(_FUSED_VJP_MODES)}, not {ctx.mode}")
         prm, q, t, rp, rd, p_final, traj, nexec, normal_u, *leaves = ctx.saved_tensors
+        table = leaves.pop() if ctx.table_saved else None
         cs, dev = ctx.cs, rp.device
         g = _f32c(grad_image)
         gtheta = None
@@ -668,7 +702,11 @@ class Render(torch.autograd.Function):
             # modes 3, 6, 7 (and a user shader) use the pose quaternion in the shader itself: per-ray dL/dq, summed per camera below
             gqdir = torch.empty(p_final.shape[:-1] + (4,), dtype=torch.float32, device=dev) \
                 if (ctx.needs_input_grad[1] and ctx.mode in (3, 6, 7, _abi.MODE_USER)) else None
-            cmap = ctx.cmap if ctx.mode in (6, 7) else None
+            cmap = ctx.cmap if ctx.mode in (6, 7) else table       # (a user shader's lookup table travels in the colormap slot)
+            # ... and where it wants a gradient, the fused backward leaves T (row, dL/d(row)) records per pixel for rm_table_scatter
+            taps = cs.user_shader_table_taps
+            records = torch.empty((p_final.numel() // 3, taps, 4), dtype=torch.float32, device=dev) \
+                if (table is not None and ctx.needs_input_grad[_CMAP_ARG]) else None
             # deferred-ray workspace: room for one ray in eight (config 4 defers 2 %; the rest is walked in place)
             hard_cap = 0 if (bwd_hard_capacity == 0 or ctx.steps == 0) else \
                 (bwd_hard_capacity or min(1 << 21, max(4096, p_final.numel() // 3 // 8)))
@@ -676,15 +714,20 @@ class Render(torch.autograd.Function):
                 if hard_cap else None
             if bwd_tile_cost_sink is not None:             # measurement runs: word 32 of `work` = rays deferred
                 globals()["bwd_last_work"], globals()["bwd_last_hard"] = work, (hard, hard_cap)
-            _abi.check(lib.rm_render_backward(s, cam, ctx.tetra, _abi.ptr(q), _abi.ptr(t), _abi.ptr(traj),
-                                               _abi.ptr(nexec), _abi.ptr(p_final), _abi.ptr(normal_u), _abi.ptr(g), _abi.ptr(gprm),
-                                               _abi.ptr(part), _abi.ptr(work), _abi.ptr(gpos), _abi.ptr(gdirs),
-                                               _abi.ptr(gqdir), _abi.ptr(cmap), 0 if cmap is None else cmap.shape[0],
-                                               0 if cmap is None else _abi.dtype_code(cmap.dtype),
-                                               ctx.mode, ctx.degree, ctx.steps, ctx.rows[0], ctx.rows[1],
-                                               ctx.flags & ~bwd_clear_flags,
-                                               _abi.ptr(bwd_tile_cost_sink), _abi.ptr(hard), hard_cap, stream),
-                       "rm_render_backward", lib)
+            args = (s, cam, ctx.tetra, _abi.ptr(q), _abi.ptr(t), _abi.ptr(traj),
+                    _abi.ptr(nexec), _abi.ptr(p_final), _abi.ptr(normal_u), _abi.ptr(g), _abi.ptr(gprm),
+                    _abi.ptr(part), _abi.ptr(work), _abi.ptr(gpos), _abi.ptr(gdirs),
+                    _abi.ptr(gqdir), _abi.ptr(cmap), 0 if cmap is None else cmap.shape[0],
+                    0 if cmap is None else _abi.dtype_code(cmap.dtype),
+                    ctx.mode, ctx.degree, ctx.steps, ctx.rows[0], ctx.rows[1],
+                    ctx.flags & ~bwd_clear_flags,
+                    _abi.ptr(bwd_tile_cost_sink), _abi.ptr(hard), hard_cap)
+            gtable = None
+            if records is None:
+                _abi.check(lib.rm_render_backward(*args, stream), "rm_render_backward", lib)
+            else:
+                _abi.check(lib.rm_render_backward_table(*args, _abi.ptr(records), stream), "rm_render_backward_table", lib)
+                gtable = table_scatter(records, table.shape[0], stream)
         if gtheta is not None and cs.user_shader[1]:
             gprm[cs.shader_offset:cs.shader_offset + cs.user_shader[1]] += gtheta[:cs.user_shader[1]]
         gq = gt = None
@@ -709,7 +752,9 @@ class Render(torch.autograd.Function):
                 if p.dim() != 1:
                     g = g.view(p.shape)
                 leaf_grads.append(g if p.dtype == torch.float32 else g.to(p.dtype))
-        return (gp_out, gq, gt) + (None,) * (_N_FIXED_ARGS - 3) + tuple(leaf_grads)
+        fixed = [gp_out, gq, gt] + [None] * (_N_FIXED_ARGS - 3)
+        fixed[_CMAP_ARG] = gtable
+        return tuple(fixed) + tuple(leaf_grads)
 
 
 _NO_GRAD = (False,) * 3
@@ -723,7 +768,8 @@ def render_frame(params, orientation, translation, cs: CompiledScene, ray_positi
     ``event_sink`` (inference frames): a list that receives a (start, end) pair of timing events recorded on the
     launch stream immediately around rm_render_forward."""
     if torch.is_grad_enabled() and ((params is not None and params.requires_grad) or orientation.requires_grad
-                                    or translation.requires_grad or any(p.requires_grad for p in leaves)):
+                                    or translation.requires_grad or any(p.requires_grad for p in leaves)
+                                    or (cmap is not None and cmap.requires_grad and user_table(cs, mode))):
         return Render.apply(params, orientation, translation, cs, ray_positions, ray_directions, tetra, cmap, mode,
                             degree, steps, rows, flags, allreduce_minmax, precision, image_dtype, tile_order, tile_cost,
                             *leaves)

@@ -176,7 +176,8 @@ def _shader_section(cs: CompiledScene) -> str:
     four, of which user_shader_fwd / user_shader_vjp then carry the probe values; the probe pair of a chained shader
     (RM_USER_SHADER_PROBES_CHAINED) also carries the history ``h`` of the values before probe ``k`` and, in the VJP, ``gh``.  A shader
     normalised by the frame's min / max (RM_USER_SHADER_NORMALISE) adds user_shader_finish / user_shader_finish_vjp, the second
-    pass; every other header is, byte for byte, what it was without them."""
+    pass; every other header is, byte for byte, what it was without them.  A shader that reads a lookup table (RM_USER_SHADER_TABLE,
+    RM_USER_SHADER_TABLE_TAPS; never with probes or a second pass) has user_shader_fwd / user_shader_vjp carry ``tab`` (and ``gt``)."""
     text = _shader_passes(cs)
     if not cs.user_shader_normalise:
         return text
@@ -197,6 +198,16 @@ def _shader_passes(cs: CompiledScene) -> str:
     head = ("#define RM_USER_SHADER 1\n"
             f"#define RM_USER_SHADER_THETA {cs.shader_offset}\n"
             f"#define RM_USER_SHADER_PARAMS {floats}\n")
+    if cs.user_shader_table:        # (register_shader(table=..., table_taps=T): never with probes; the pair carries tab and gt)
+        return (
+            head + "#define RM_USER_SHADER_TABLE 1\n" + f"#define RM_USER_SHADER_TABLE_TAPS {cs.user_shader_table_taps}\n"
+            + f"// user shader: {name}, {floats} parameter floats, a lookup table of {cs.user_shader_table_taps} taps, sha1 {sha}\n"
+            + f"{cs.user_shader_source.strip()}\n"
+            "template <bool Fast> RM_DEV V3 user_shader_fwd(const ShadeIn& s, const float* theta, const Table& tab) {\n"
+            f"  return {name}_fwd<Fast>(s, theta, tab);\n}}\n"
+            "template <bool Fast> RM_DEV void user_shader_vjp(const ShadeIn& s, const float* theta, const Table& tab, V3 g, ShadeGrad& gs, "
+            "float* gtheta, TableGrad& gt) {\n"
+            f"  {name}_vjp<Fast>(s, theta, tab, g, gs, gtheta, gt);\n}}\n")
     if not k:
         return (
             head
