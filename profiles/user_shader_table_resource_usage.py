@@ -6,7 +6,9 @@ next to those of a table-less shader's (no GPU needed):
 
   depth_cue            make_test_scene2() with contrib.DepthCueShader: no table.  Its rows are the evidence that libraries without a
                        table are what they were: profiles/user_shader_table_parent_depth_cue.txt holds the same rows from the commit
-                       before lookup tables, and tests/test_user_shader_table.py compares the two.
+                       before lookup tables, and tests/test_user_shader_table.py compares the two.  (Both files are
+                       re-recorded whenever the frame kernels themselves change, as with the march in groups: the
+                       depth_cue rows are then this tree's, and the comparison holds the two files to each other.)
   depth_palette        ... with contrib.DepthPaletteShader: T = 2, the fused backward stores two records per pixel
   tangent_palette      ... with contrib.TangentPaletteShader: T = 1
 and k_table_scatter, which every library carries.  Compiled exactly as ray_marching_amd/specialize.py does, plus

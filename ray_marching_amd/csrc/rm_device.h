@@ -296,6 +296,9 @@ struct RegParams {
 #ifndef RM_CULL_TRACKED
 #define RM_CULL_TRACKED 2   // cull sites per scene whose decision is carried from step to step (2 VGPRs each)
 #endif
+#ifndef RM_GROUP_UNROLL_MAX_INS
+#define RM_GROUP_UNROLL_MAX_INS 64   // programs up to this length get the four steps of a march group as four copies (march_groups)
+#endif
 
 template <class Store, bool Fast = false>
 struct Fwd {
@@ -951,6 +954,7 @@ struct Ins {
 struct RuntimeProgram {
   static constexpr int kTracked = 0;     // the interpreter always runs the full cull test
   static constexpr bool kNeedsFullWave = true;   // may contain CULL_LSE (wave-wide DPP reductions: every lane active)
+  static constexpr bool kUnrollGroups = false;    // march_groups: one copy of the interpreter loop, run four times
   const int4* code;
   int n;
   template <class S, class PT>
@@ -1029,6 +1033,8 @@ struct StaticProgram {
     return false;
   }
   static constexpr bool kNeedsFullWave = has_wave_reductions();   // the DPP reductions of the table tests need every lane of the wave active
+  // march_groups copies the evaluation four times (one per step of a group) for programs up to this length
+  static constexpr bool kUnrollGroups = Code::n <= RM_GROUP_UNROLL_MAX_INS;
   // does the smooth union that ends at `pc` carry a bound table (exact culling of its children, RM_OP_CULL_LSE)?
   static constexpr bool smooth_culled(int pc) {
     int depth = 0;

@@ -338,12 +338,26 @@ RM_DEV int park_stride(int steps) { return steps <= 128 ? 16 : ((steps + 127) / 
 // `park(step, p_next, unsettled)`: called wave-wide at a check step when 1..RM_PARK_MAX_LANES rays of the wave are
 // not yet in a proven cycle; returns (per lane) whether the ray was put on a list -- it then belongs to
 // k_render_parked and this wave neither waits for it nor stores its pixel (`parked` out).
-template <class SceneT, class ParkF = NoPark, bool kSoa = false>
+// kMayRecord = false: the caller never records a trajectory (`traj` is not looked at).
+//
+// Two loops walk the same march.  The stepwise one defines it: one step per trip, and per trip the tests that decide
+// what the step is (priority step, knowledge drop, look cadence, last step).  The grouped one runs in front of it when
+// the early-out is on, nothing is parked and there are at least RM_EARLY_DENSE_STEPS steps: RM_EARLY_DENSE_STEPS / 2
+// trips of two steps and a look, then trips of four steps and one look, the steps of a trip running from step_point
+// straight into the next evaluation.  Of the per-step tests it keeps those a trip can meet (a group starts at a multiple
+// of four: the knowledge drop at its first step, the priority step at step RM_PRIO_TILE & 3 of it), once per trip.
+// Fewer than four steps left over carry no look in either loop: the stepwise loop walks them with the looks off.
+// The steps of a group are four copies of the evaluation in the frame kernels (kSoa) of static programs of up to
+// RM_GROUP_UNROLL_MAX_INS instructions, one copy in a loop of four otherwise (the interpreter, programs too long to
+// copy, k_march_fwd: where the copies cost a wave per SIMD).
+template <class SceneT, class ParkF = NoPark, bool kSoa = false, bool kMayRecord = true>
 RM_DEV V3 march(const SceneT& scene, V3 p, V3 v, int steps, bool early, float* traj, int64_t traj_stride,
                 int64_t ray, bool live, int& nexec, ParkF park = ParkF(), bool* parked = nullptr) {
+  constexpr int kDense = RM_EARLY_DENSE_STEPS, kPrio = RM_PRIO_TILE;
   if (parked) *parked = false;
   const int pstride = park_stride(steps);
   V3 snap = p;          // remembered iterate p_s (per lane)
+  V3 prev = p;          // the iterate before p
   int snap_step = 0;    // s            (wave-uniform: every lane refreshes at the same steps)
   int next_snap = 2;    // refresh the snapshot when the step index reaches this (2, 4, 8, ...)
   int lambda = 0;       // cycle length of this ray, 0 = not known yet
@@ -353,65 +367,114 @@ RM_DEV V3 march(const SceneT& scene, V3 p, V3 v, int steps, bool early, float* t
   // drift of p cannot accumulate beyond the slack folded into the bound (derive_constants)
   const float vn = 1.0001f * __builtin_amdgcn_sqrtf(__builtin_fmaf(v.z, v.z, __builtin_fmaf(v.y, v.y, v.x * v.x)));
   float move = __builtin_nanf("");
-#if RM_PRIO_TILE > 0
-  __builtin_amdgcn_s_setprio(0);
-#endif
-  for (int i = 0; i < steps; ++i) {
-#if RM_PRIO_TILE > 0
-    // a tile still marching by now is one of those that decide when the launch ends: its wave is issued first from
-    // here on (measured, profiles/regen_probe.py: 32-primitive 8K band 11.45 -> 10.65 ms, 1080p scene 2 208 -> 204 us)
-    if (i == RM_PRIO_TILE) __builtin_amdgcn_s_setprio(3);
-#endif
-    if (traj && live) traj_store<kSoa>(traj, traj_stride, ray, i, p);
-    float f = scene.eval_near(p, (i & 15) ? move : __builtin_nanf(""));
+  if (kPrio > 0) __builtin_amdgcn_s_setprio(0);
+  // step i: p <- f(p) v + p, where p is at most `known` away from the point of the previous evaluation (NaN: not known)
+  auto step = [&](int i, float known) {
+    // compiler-only barrier: no memory access of one step is moved into or shared with the next, as in a loop of single
+    // steps (without it the recording frame kernel of the closed scene compiled to 129 VGPRs, 3 waves per SIMD
+    // instead of 4; profiles/march_groups_ab.txt)
+    __asm__ volatile("" ::: "memory");
+    if constexpr (kMayRecord) {
+      if (traj && live) traj_store<kSoa>(traj, traj_stride, ray, i, p);
+    }
+    const float f = scene.eval_near(p, known);
     move = __builtin_fmaf(fabsf(f), vn, 4e-6f);
-    V3 pn = step_point(p, v, f);
-    const int cadence = (i < RM_EARLY_DENSE_STEPS) ? 1 : 3;
-    if (early && (i & cadence) == cadence) {
-      // Looked at after every second step at first and after every fourth from step RM_EARLY_DENSE_STEPS on
-      // (measured: 8 -> 9.35 Grays/s, 16 -> 9.3, 32 -> 9.1, every second step throughout -> 8.8; a third
-      // level, every eighth step from 64 on, bought nothing).  The candidate periods i + 1 - s are then
-      // multiples of 2 or 4: a multiple of the true period serves `remaining mod lambda` just as well, and
-      // a fixed point is a cycle of any length; a wave leaves at most 3 steps later than it could.
-      // branch-free per-lane bookkeeping (selects, no exec-mask juggling)
-      const bool fixed = same_bits(pn, p);
-      // (also while a trajectory is recorded: the reverse sweep then reads p_final for every step >= nexec, which
-      // is what a cycle between neighbouring floats is up to an ulp or two -- far inside the tolerance tau of its
-      // converged-tail handling, march_reverse)
-      const bool cyc = same_bits(pn, snap);
-      const int found = fixed ? 1 : (cyc ? (i + 1 - snap_step) : 0);
-      lambda = (lambda == 0) ? found : lambda;
-      if constexpr (ParkF::kEnabled) {
-        // a minority of the tile's rays still moving at a check step: hand them over instead of keeping 64 lanes
-        // (and the whole wave's issue slots) busy for them
-        const int done = i + 1;
-        if (!traj && done >= RM_PARK_FIRST * pstride && done < steps && done % pstride == 0) {
-          const bool unsettled = live && lambda == 0;
-          const int cnt = __popcll(__ballot(unsettled));
-          if (cnt > 0 && cnt <= RM_PARK_MAX_LANES) {
-            const bool gone = park(done, pn, unsettled);
-            if (gone) { *parked = true; lambda = 1; }          // no longer waited for; its pixel is not ours any more
-          }
+    prev = p;
+    p = step_point(p, v, f);
+  };
+  // The look after step `done`; true when every ray of the wave has a proven period (nexec = done).
+  // Looked at after every second step at first and after every fourth from step RM_EARLY_DENSE_STEPS on
+  // (measured: 8 -> 9.35 Grays/s, 16 -> 9.3, 32 -> 9.1, every second step throughout -> 8.8; a third
+  // level, every eighth step from 64 on, bought nothing).  The candidate periods done - s are then
+  // multiples of 2 or 4: a multiple of the true period serves `remaining mod lambda` just as well, and
+  // a fixed point is a cycle of any length; a wave leaves at most 3 steps later than it could.
+  auto look = [&](int done) {
+    // branch-free per-lane bookkeeping (selects, no exec-mask juggling)
+    const bool fixed = same_bits(p, prev);
+    // (also while a trajectory is recorded: the reverse sweep then reads p_final for every step >= nexec, which
+    // is what a cycle between neighbouring floats is up to an ulp or two -- far inside the tolerance tau of its
+    // converged-tail handling, march_reverse)
+    const bool cyc = same_bits(p, snap);
+    const int found = fixed ? 1 : (cyc ? (done - snap_step) : 0);
+    lambda = (lambda == 0) ? found : lambda;
+    if constexpr (ParkF::kEnabled) {
+      // a minority of the tile's rays still moving at a check step: hand them over instead of keeping 64 lanes
+      // (and the whole wave's issue slots) busy for them
+      if (!traj && done >= RM_PARK_FIRST * pstride && done < steps && done % pstride == 0) {
+        const bool unsettled = live && lambda == 0;
+        const int cnt = __popcll(__ballot(unsettled));
+        if (cnt > 0 && cnt <= RM_PARK_MAX_LANES) {
+          const bool gone = park(done, p, unsettled);
+          if (gone) { *parked = true; lambda = 1; }          // no longer waited for; its pixel is not ours any more
         }
-      }
-      if (__all(lambda > 0)) {
-        nexec = i + 1;
-        int need = (steps - (i + 1)) % lambda;    // further steps this lane still has to take
-        p = pn;
-        while (__any(need > 0)) {                 // < max lambda iterations; lanes freeze when done
-          float g = scene.eval(p);
-          V3 q = mk3(g * v.x + p.x, g * v.y + p.y, g * v.z + p.z);
-          if (need > 0) p = q;
-          --need;
-        }
-        return p;
-      }
-      if (i + 1 == next_snap) {                   // scalar condition; lanes that already know their
-        snap = pn; snap_step = i + 1;             // period no longer look at the snapshot
-        next_snap <<= 1;
       }
     }
-    p = pn;
+    if (__all(lambda > 0)) {
+      nexec = done;
+      return true;
+    }
+    if (done == next_snap) {                      // scalar condition; lanes that already know their
+      snap = p; snap_step = done;                 // period no longer look at the snapshot
+      next_snap <<= 1;
+    }
+    return false;
+  };
+  int i = 0;
+  bool left = false;
+  if constexpr (!ParkF::kEnabled && kDense % 4 == 0) {
+    if (early && steps >= kDense) {
+      // i even: of the two steps of a trip only the first can be a multiple of 16
+      auto pair = [&]() {
+        if (kPrio > 0 && kPrio < kDense && (kPrio & 1) == 0 && i == kPrio) __builtin_amdgcn_s_setprio(3);
+        step(i, (kDense > 16 && (i & 15) == 0) ? __builtin_nanf("") : move);      // (step 0: move = NaN)
+        if (kPrio > 0 && kPrio < kDense && (kPrio & 1) == 1 && i + 1 == kPrio) __builtin_amdgcn_s_setprio(3);
+        step(i + 1, move);
+        return look(i + 2);
+      };
+      // (unrolled in the recording frame kernel of a program short enough to copy, rolled everywhere else: the
+      // combination at which no kernel loses a wave per SIMD, profiles/march_groups_ab.txt)
+      if constexpr (kSoa && kMayRecord && decltype(scene.prog)::kUnrollGroups) {
+#pragma unroll
+        for (; i < kDense; i += 2)
+          if (pair()) { left = true; break; }
+      } else {
+#pragma nounroll
+        for (; i < kDense; i += 2)
+          if (pair()) { left = true; break; }
+      }
+      auto grouped = [&](int j) {
+        if (kPrio >= kDense && (kPrio & 3) == j && i + j == kPrio) __builtin_amdgcn_s_setprio(3);
+        step(i + j, (j == 0 && (i & 15) == 0) ? __builtin_nanf("") : move);
+      };
+      for (; !left && i + 4 <= steps; i += 4) {
+        if constexpr (kSoa && decltype(scene.prog)::kUnrollGroups) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) grouped(j);
+        } else {
+#pragma nounroll
+          for (int j = 0; j < 4; ++j) grouped(j);
+        }
+        if (look(i + 4)) { left = true; break; }
+      }
+      early = false;                              // what is left is fewer than four steps: no look falls on them
+    }
+  }
+  for (; !left && i < steps; ++i) {
+    // a tile still marching by now is one of those that decide when the launch ends: its wave is issued first from
+    // here on (measured, profiles/regen_probe.py: 32-primitive 8K band 11.45 -> 10.65 ms, 1080p scene 2 208 -> 204 us)
+    if (kPrio > 0 && i == kPrio) __builtin_amdgcn_s_setprio(3);
+    step(i, (i & 15) ? move : __builtin_nanf(""));
+    const int cadence = (i < kDense) ? 1 : 3;
+    if (early && (i & cadence) == cadence && look(i + 1)) { left = true; break; }
+  }
+  if (left) {
+    int need = (steps - nexec) % lambda;          // further steps this lane still has to take
+    while (__any(need > 0)) {                     // < max lambda iterations; lanes freeze when done
+      float g = scene.eval(p);
+      V3 q = mk3(g * v.x + p.x, g * v.y + p.y, g * v.z + p.z);
+      if (need > 0) p = q;
+      --need;
+    }
   }
   return p;
 }
@@ -1481,9 +1544,9 @@ __global__ void __launch_bounds__(256) k_render_fwd(RenderArgs a) {
     bool parked;
     // (a recorded trajectory is indexed by the wave tile's slot, not by the pixel: traj_store<true>)
     float* const traj = kRecord ? a.traj : nullptr;
-    V3 p = march<decltype(scene), ParkToList, true>(scene, r.o, r.v, a.steps, early, traj, a.steps,
-                                                    traj ? tile * 64 + (threadIdx.x & 63) : r.li, r.live, nexec,
-                                                    ParkToList{a, r.li}, &parked);
+    V3 p = march<decltype(scene), ParkToList, true, kRecord>(scene, r.o, r.v, a.steps, early, traj, a.steps,
+                                                             traj ? tile * 64 + (threadIdx.x & 63) : r.li, r.live, nexec,
+                                                             ParkToList{a, r.li}, &parked);
     if (a.tile_cost && (threadIdx.x & 63) == 0) a.tile_cost[tile] = nexec;     // nexec is wave-uniform
     r.live = r.live && !parked;                 // a parked ray's pixel is written by k_render_parked
     finish_tile<decltype(scene), kRecord>(a, scene, T, r, p, nexec, mm);
