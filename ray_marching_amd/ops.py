@@ -217,8 +217,16 @@ class March(torch.autograd.Function):
         cs, dev, steps = ctx.cs, v.device, ctx.steps
         n = v.shape[0]
         g = _f32c(grad_out.expand(ctx.shape)).reshape(-1, 3)
-        if steps == 0 or n == 0:
-            return torch.zeros_like(prm), grad_out, torch.zeros_like(grad_out), None, None, None
+
+        def fit(t, shape):
+            """A gradient over the broadcast rays, summed back into an input's own shape."""
+            t = t.view(ctx.shape).to(ctx.in_dtype)
+            return t.sum_to_size(shape) if tuple(shape) != tuple(ctx.shape) else t
+
+        if steps == 0 or n == 0:         # the output is the (broadcast) origin: nothing reaches the directions or the scene
+            return (torch.zeros_like(prm), fit(g, ctx.pos_shape) if ctx.needs_input_grad[1] else None,
+                    torch.zeros(ctx.dirs_shape, dtype=ctx.in_dtype, device=dev) if ctx.needs_input_grad[2] else None,
+                    None, None, None)
         gpos = torch.empty_like(v)
         gdirs = torch.empty_like(v) if ctx.needs_input_grad[2] else None
         gprm = torch.empty(max(cs.n_params, 1), dtype=torch.float32, device=dev)
@@ -228,11 +236,6 @@ class March(torch.autograd.Function):
             _ck(cs, cs.lib(True).rm_march_backward(s, _abi.ptr(v), _abi.ptr(traj), _abi.ptr(nexec), _abi.ptr(g),
                                               _abi.ptr(gpos), _abi.ptr(gdirs), _abi.ptr(gprm), _abi.ptr(part),
                                               n, steps, _abi.current_stream(dev)), "rm_march_backward")
-
-        def fit(t, shape):
-            t = t.view(ctx.shape).to(ctx.in_dtype)
-            return t.sum_to_size(shape) if tuple(shape) != tuple(ctx.shape) else t
-
         return (gprm[: prm.numel()], fit(gpos, ctx.pos_shape),
                 fit(gdirs, ctx.dirs_shape) if gdirs is not None else None, None, None, None)
 
@@ -278,6 +281,9 @@ class Normals(torch.autograd.Function):
         pts = pts.float()
         cs, dev = ctx.cs, pts.device
         n = pts.shape[0]
+        if n == 0:
+            lead = grad_n.shape[:-1] if grad_n is not None else grad_lap.shape[:-1]
+            return torch.zeros_like(prm), torch.zeros(*lead, 3, dtype=ctx.in_dtype, device=dev), None, None
         gn = _f32c(grad_n).reshape(-1, 3) if grad_n is not None else None
         gl = _f32c(grad_lap).reshape(-1) if grad_lap is not None else None
         gpts = torch.empty_like(pts) if ctx.needs_input_grad[1] else None

@@ -46,6 +46,19 @@ def load_cyclic_cmap() -> Tensor:
     return default_cyclic_cmap()
 
 
+def _vignette_pixels_per_camera(lead, n: int, frames: Tensor) -> int:
+    """How many consecutive pixels take one pixel frame in the vignette shader.  One frame serves every pixel, whatever the
+    leading shape (the reference's broadcast of ``frames[..., 2]``); N > 1 frames need the camera axis in front, [N, ..., 3]:
+    flattened rays carry none, and the kernels would read every pixel against frame 0 (or past the last frame)."""
+    cams = frames.numel() // 9
+    if cams <= 1:
+        return max(n, 1)
+    if len(lead) < 2 or lead[0] != cams:
+        raise ValueError(f"vignette shader: {cams} pixel frames need ray_directions with the camera axis in front, "
+                         f"[{cams}, ..., 3]; got {list(lead) + [3]}")
+    return n // cams
+
+
 def shade(mode: int, degree: int = 1, *, px_coords=None, orientation=None, frames=None, dirs=None,
           coords=None, normals=None, lap=None, dist=None, cmap=None, allreduce_minmax=None) -> Tensor:
     """Run one shader mode over tensors; returns [..., 1] (modes 0,1,2,3,5) or [..., 3]."""
@@ -61,6 +74,8 @@ def shade(mode: int, degree: int = 1, *, px_coords=None, orientation=None, frame
     for d in lead:
         n *= d
     per_cam = n // lead[0] if len(lead) > 1 else n
+    if mode == 3 and frames is not None:
+        per_cam = _vignette_pixels_per_camera(lead, n, frames)
 
     def flat(t, ch):
         return None if t is None else _f32c(t.expand(*lead, ch)).reshape(-1, ch)
@@ -136,6 +151,8 @@ class _PixelShade(torch.autograd.Function):
         for d in lead:
             n *= d
         per_cam = n // lead[0] if len(lead) > 1 else n
+        if ctx.mode == 3 and frames is not None:
+            per_cam = _vignette_pixels_per_camera(lead, n, frames)
         ch = 3 if ctx.mode == 4 else 1
         g = _f32c(grad.expand(*lead, ch)).reshape(-1, ch)
         d32 = None if dirs is None else _f32c(dirs.expand(*lead, 3)).reshape(-1, 3)

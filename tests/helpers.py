@@ -300,3 +300,106 @@ def random_blob_spec(gen, n_min=8, n_max=40):
         return ("union", {}, [room, blob]), spread
     q = torch.nn.functional.normalize(torch.randn(4, generator=gen), dim=0)
     return ("union", {}, [("affine", {"translation": u(-1.0, 1.0, 3), "orientation": q}, blob), random_spec(gen, depth=2)]), spread
+
+
+# --------------------------------------------------------------------------
+# the rule of tests/test_standalone_backward.py: the exact build's stand-alone gradients against CPU autograd on the oracle
+# --------------------------------------------------------------------------
+# One gradient tensor against the oracle's float32 and float64 autograd on the same inputs: the project's gradient contract
+# (1e-4, relative to the largest float64 component once that exceeds 1) with the min rule of test_backward_vs_golden -- the
+# nearer of the two references counts, since float32 autograd carries its own rounding and float64 follows another trajectory
+# where float32 rounds.  Non-finite elements are float32's business alone (float64 does not overflow where float32 does).
+STANDALONE_WORST = {}      # group -> [(|got - g32|, what), (|got - g64|, what), (|g32 - g64|, what)], printed as it grows
+
+
+def f64_spec(spec):
+    return O.map_spec(spec, lambda x: x.detach().double())
+
+
+def standalone_note(group, what, figures):
+    worst = STANDALONE_WORST.setdefault(group, [(0.0, "")] * 3)
+    for k, x in enumerate(figures):
+        if x > worst[k][0]:
+            worst[k] = (x, what)
+
+
+def standalone_summary():
+    lines = []
+    for group in sorted(STANDALONE_WORST):
+        (a, wa), (b, wb), (c, wc) = STANDALONE_WORST[group]
+        lines.append(f"stand-alone gradients [{group}]: worst |got - g32| {a:.3g} ({wa}), |got - g64| {b:.3g} ({wb}), "
+                     f"|g32 - g64| {c:.3g} ({wc})")
+    return lines
+
+
+def gradient_contract(group, what, got, g32, g64, tol=1e-4, absolute=False):
+    """min(max|got - g32|, max|got - g64|) <= tol max(1, max|g64|) over the elements finite in the references (``absolute``:
+    <= tol, the bound the point gradients of scene(points) have always had); NaN exactly where the float32 oracle has NaN,
+    and equal to it where that is infinite.  Prints the three figures before it asserts; -> min(e32, e64)."""
+    got, g32, g64 = (torch.as_tensor(x).detach().double().cpu() for x in (got, g32, g64))
+    assert got.shape == g32.shape == g64.shape, (what, got.shape, g32.shape, g64.shape)
+    nan_got, nan_ref = torch.isnan(got), torch.isnan(g32)
+    assert torch.equal(nan_got, nan_ref), f"{what}: NaN at {int(nan_got.sum())} of {got.numel()} elements, the float32 oracle at " \
+                                          f"{int(nan_ref.sum())}; {int((nan_got != nan_ref).sum())} positions differ"
+    inf = torch.isinf(g32)
+    assert torch.equal(got[inf], g32[inf]), (what, "infinite elements differ")
+    fin32 = torch.isfinite(g32)
+    fin = fin32 & torch.isfinite(g64)
+    e32 = float((got - g32)[fin32].abs().max()) if bool(fin32.any()) else 0.0
+    e64 = float((got - g64)[fin].abs().max()) if bool(fin.any()) else 0.0
+    spread = float((g32 - g64)[fin].abs().max()) if bool(fin.any()) else 0.0
+    scale = 1.0 if absolute or not bool(fin.any()) else max(1.0, float(g64[fin].abs().max()))
+    print(f"{what}: |got - g32| {e32:.3g}, |got - g64| {e64:.3g}, |g32 - g64| {spread:.3g}, scale {scale:.3g}, "
+          f"{int(nan_ref.sum())} NaN of {got.numel()}")
+    standalone_note(group, what, (e32, e64, spread))
+    best = min(e32, e64) if bool(fin.any()) else e32
+    assert best <= tol * scale, (what, e32, e64, spread, scale)
+    return best
+
+
+def fp16_gradient_contract(group, what, got, g32, g64, tol=1e-4):
+    """gradient_contract for a gradient handed back in fp16: the fp32 gradient rounded once, so each element may sit half an
+    fp16 ulp (2^-11 relative, 2^-25 among the subnormals) further from the reference than the contract allows."""
+    assert got.dtype == torch.float16, (what, got.dtype)
+    got, g32, g64 = (torch.as_tensor(x).detach().double().cpu() for x in (got, g32, g64))
+    assert got.shape == g32.shape == g64.shape, (what, got.shape, g32.shape, g64.shape)
+    assert bool(torch.isfinite(g32).all()) and bool(torch.isfinite(g64).all()) and bool(torch.isfinite(got).all()), what
+    scale = max(1.0, float(g64.abs().max()))
+    beyond = [float(((got - ref).abs() - (2.0 ** -11 * ref.abs() + 2.0 ** -25)).clamp(min=0.0).max()) for ref in (g32, g64)]
+    print(f"{what}: beyond fp16 rounding |got - g32| {beyond[0]:.3g}, |got - g64| {beyond[1]:.3g}, |g32 - g64| "
+          f"{float((g32 - g64).abs().max()):.3g}, scale {scale:.3g}")
+    standalone_note(group, what, (beyond[0], beyond[1], float((g32 - g64).abs().max())))
+    assert min(beyond) <= tol * scale, (what, beyond, scale)
+    return min(beyond)
+
+
+def ulp16_distance(got, want):
+    """|got - want| in fp16 units in the last place (bit patterns as ordered integers), int64 tensor."""
+    def ordered(t):
+        b = torch.as_tensor(t).detach().cpu().contiguous()
+        assert b.dtype == torch.float16
+        b = b.view(torch.int16).long()
+        return torch.where(b < 0, -(b & 0x7fff), b)
+    return (ordered(got) - ordered(want)).abs()
+
+
+def generic_lds_floats(cs, block, backward):
+    """GenericCfg::lds_floats (csrc/rm_kernels.h) for the compiled scene ``cs``, restated."""
+    pb = (cs.n_params + cs.n_derived + 3) & ~3
+    prog = 4 * cs.n_instr
+    columns = (cs.stack_floats + cs.n_slots) * (block + 1)
+    if not backward:
+        return pb + prog + columns
+    work = columns + (cs.n_params + cs.n_grad_derived) * (block >> 6)
+    return pb + max(prog, work)
+
+
+def generic_block(cs, backward, what=""):
+    """The block pick_launch (csrc/rm_abi.hip) gives the interpreter's stand-alone kernels: the largest of 256 (backward: 128),
+    ... 64 threads whose LDS fits the default 64 KiB, else 64 with the limit raised.  Prints it."""
+    block = 128 if backward else 256
+    while block > 64 and 4 * generic_lds_floats(cs, block, backward) > 64 * 1024:
+        block >>= 1
+    print(f"launch shape {what}: {'backward' if backward else 'forward'} block {block}, "
+          f"{4 * generic_lds_floats(cs, block, backward)} B of LDS ({cs.n_params} parameters, {cs.n_instr} instructions)")
+    return block
