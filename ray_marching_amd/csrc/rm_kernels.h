@@ -625,7 +625,10 @@ RM_DEV V3 march_reverse(const SceneT& scene, V3 lam, V3 v, V3 p_final, const flo
     const float gf0 = (lam.x * v.x + lam.y * v.y) + lam.z * v.z;
     const bool active = !noise(gf0);
     if (!__any(active)) { finish_frozen(i); return lam; }
-    const bool deferred = defer(i, lam, gv, active);
+    // A ray whose adjoint is not finite (the rays of the frame's minimum and maximum in modes 1, 2, 5) stays with this wave:
+    // k_bwd_hard_a forms lambda += g n, which turns the exact zeros of n (a plane's y and z) into NaN, where the per-step
+    // VJP below leaves them alone like the reference does.
+    const bool deferred = defer(i, lam, gv, active && fabsf(gf0) <= 3.4028234664e38f);
     if (deferred) {
       if (deferred_out) *deferred_out = true;
       lam = mk3(0.0f, 0.0f, 0.0f);                 // contributes nothing below; its outputs come from k_bwd_hard_a

@@ -383,6 +383,118 @@ def ulp16_distance(got, want):
     return (ordered(got) - ordered(want)).abs()
 
 
+# --------------------------------------------------------------------------
+# the references of tests/test_tree_frame_backward.py: frames of random scene trees, differentiated by CPU autograd on the oracle
+# --------------------------------------------------------------------------
+# A bare random_spec tree is nearly always an open scene (rays leave it, every gradient is NaN), so each tree stands in a closed
+# room; the room is child 0 of the root union and the tree child 1, i.e. the tree's parameters are the "sdfs.1." ones.
+TREE_POSE = ((0.98, 0.05, -0.12, 0.03), (0.1, -0.1, -4.0))
+NODE_KINDS = ("sphere", "box", "plane", "line", "disk", "torus", "affine", "smooth_union", "union", "rounding", "onion")
+_FRAME_REFERENCES = {}
+
+
+def roomed(tree):
+    """``tree`` next to the shell of a 10 x 9 x 11 box in a min-union: a closed scene around the camera of TREE_POSE."""
+    room = ("onion", {"radius": torch.tensor(0.1)}, ("box", {"halfsides": torch.tensor([5.0, 4.5, 5.5])}))
+    return ("union", {}, [room, tree])
+
+
+def spec_key(spec):
+    """The tree and every parameter value as nested tuples: hashable, equal for equal scenes."""
+    kids = spec[2] if len(spec) > 2 else []
+    kids = kids if isinstance(kids, list) else [kids]
+    prm = tuple((k, tuple(torch.as_tensor(v).detach().double().flatten().tolist())) for k, v in spec[1].items())
+    return (spec[0], prm, tuple(spec_key(c) for c in kids))
+
+
+def frame_weights(h, w):
+    return torch.rand(1, h, w, 3, generator=torch.Generator().manual_seed(3 + h + 131 * w))
+
+
+def pose_tensors(pose, dtype=torch.float32):
+    q = torch.nn.functional.normalize(torch.tensor([pose[0]], dtype=torch.float32), dim=-1)
+    return q.to(dtype), torch.tensor([pose[1]], dtype=torch.float32).to(dtype)
+
+
+def frame_loss(image, h, w):
+    return (image * frame_weights(h, w).to(device=image.device, dtype=image.dtype)).sum() / (h * w * 3)
+
+
+def frame_gradients_cpu(spec, h, w, pose, mode, steps, dtype=torch.float32):
+    """The oracle's render of a one-camera h x w frame of ``spec`` (parameters rounded to fp32 first, then cast to ``dtype``)
+    and CPU autograd of frame_loss through it.  -> (image, {parameter name in O.spec_parameters order, ..., "orientation",
+    "translation": gradient}), all detached; a parameter the loss does not reach has a zero gradient.  Cached per (scene, frame,
+    pose, mode, steps, dtype): callers must not modify what they get."""
+    key = (spec_key(spec), h, w, pose, mode, steps, dtype)
+    if key not in _FRAME_REFERENCES:
+        live = O.map_spec(spec, lambda x: x.detach().clone().float().to(dtype).requires_grad_(True))
+        bufs = tuple(b.to(dtype) for b in O.camera_buffers(1, w, h, PX * h, PX * w, PX * h))
+        q, t = (x.requires_grad_(True) for x in pose_tensors(pose, dtype))
+        cmap = torch.from_numpy(gold("cmap.npz")["cyclic_cmap"]) if mode in (6, 7) else None
+        image = O.render(live, bufs, q, t, mode, 1, steps, EPS, cmap=cmap)
+        frame_loss(image, h, w).backward()
+        grads = {name: (torch.zeros_like(x) if x.grad is None else x.grad).detach() for name, x in O.spec_parameters(live)}
+        for name, x in (("orientation", q), ("translation", t)):
+            grads[name] = (torch.zeros_like(x) if x.grad is None else x.grad).detach()
+        _FRAME_REFERENCES[key] = (image.detach(), grads)
+    return _FRAME_REFERENCES[key]
+
+
+def admit_frame_case(spec, h, w, pose, mode, steps, tol=1e-4):
+    """Whether the oracle alone lets a frame stand as a gradient test.  Admitted when (a) the float32 image has no NaN, (b) the
+    float32 and float64 gradients have NaN at the same elements, (c) every tensor has |g32 - g64| <= tol max(1, max|g64|) on its
+    finite elements, (d) at least a third of all gradient components are finite and some parameter of the tree -- not only of
+    the room -- has a non-zero one.  -> (admitted, reason, largest |g32 - g64| / max(1, max|g64|) over the tensors)."""
+    i32, g32 = frame_gradients_cpu(spec, h, w, pose, mode, steps, torch.float32)
+    _, g64 = frame_gradients_cpu(spec, h, w, pose, mode, steps, torch.float64)
+    if bool(i32.isnan().any()):
+        return False, f"{int(i32.isnan().sum())} NaN in the float32 image", float("nan")
+    finite = total = 0
+    worst, tree = 0.0, False
+    for name, a in g32.items():
+        a, b = a.double(), g64[name]
+        if not torch.equal(a.isnan(), b.isnan()):
+            return False, f"{name}: NaN pattern of float32 and float64 differs", float("nan")
+        fin = torch.isfinite(a) & torch.isfinite(b)
+        total += a.numel()
+        finite += int(fin.sum())
+        if bool(fin.any()):
+            worst = max(worst, float((a - b)[fin].abs().max()) / max(1.0, float(b[fin].abs().max())))
+            tree = tree or (name.startswith("sdfs.1.") and bool((a[fin] != 0).any()))
+    if worst > tol:
+        return False, f"|g32 - g64| is {worst:.3g} of the scale", worst
+    if 3 * finite < total:
+        return False, f"{finite} of {total} gradient components finite", worst
+    if not tree:
+        return False, "no parameter of the tree has a non-zero gradient", worst
+    return True, "", worst
+
+
+def spec_nodes(spec, ancestors=()):
+    """Every node of the tree with the kinds above it, root first: [(node, (kind of the root, ..., kind of its parent))]."""
+    kids = spec[2] if len(spec) > 2 else []
+    kids = kids if isinstance(kids, list) else [kids]
+    return [(spec, ancestors)] + [x for c in kids for x in spec_nodes(c, ancestors + (spec[0],))]
+
+
+def spec_shapes(spec):
+    """Which of the shapes the reverse pass treats specially occur in ``spec``: a subset of {"union of one", "smooth union of
+    one", "rounding over onion", "onion over smooth union", "affine chain of three"} (three affine frames open at once: an affine
+    node with two affine nodes among its ancestors)."""
+    found = set()
+    for node, above in spec_nodes(spec):
+        kind = node[0]
+        if kind in ("union", "smooth_union") and len(node[2]) == 1:
+            found.add("union of one" if kind == "union" else "smooth union of one")
+        if kind == "rounding" and node[2][0] == "onion":
+            found.add("rounding over onion")
+        if kind == "onion" and node[2][0] == "smooth_union":
+            found.add("onion over smooth union")
+        if kind == "affine" and above.count("affine") >= 2:
+            found.add("affine chain of three")
+    return found
+
+
 def generic_lds_floats(cs, block, backward):
     """GenericCfg::lds_floats (csrc/rm_kernels.h) for the compiled scene ``cs``, restated."""
     pb = (cs.n_params + cs.n_derived + 3) & ~3
