@@ -1,11 +1,14 @@
 """Compiler-reported resources of the kernels that march, for the three libraries the grouped march (march_groups,
 rm_kernels.h) is judged on (no GPU needed):
 
-    python profiles/march_groups_resource_usage.py [--asm DIR] [--only scene2,closed1] > table.txt
+    python profiles/march_groups_resource_usage.py [--asm DIR] [--only scene2,closed1] [--all] > table.txt
 
   scene2     make_test_scene2()                 the headline frame
   closed1    make_closed_test_scene()           the training scene
   many32     make_many_primitive_scene(32)      the long program (its evaluation is not copied per step of a group)
+  generic    the interpreter's library          (only with --all or when named in --only)
+  fast       the interpreter's library, precision="fast"     (likewise)
+--all lists every kernel of every library, the backward kernels included, not only those that march.
 Compiled exactly as ray_marching_amd/specialize.py does (RM_HIPCC_EXTRA included), plus -Rpass-analysis=kernel-resource-usage.
 --asm DIR also leaves the device assembly of each library there (<name>.s) and prints, per kernel, its instruction
 counts by class and its code size as the assembler's own symbol size comment gives it."""
@@ -30,13 +33,16 @@ def short_name(mangled):
     return re.sub(r"StaticCfg<RmStaticCode, (\d+), (false|true)>", r"S\1", short)
 
 
-def resources(cs, asm=None):
+def resources(cs, asm=None, precision="exact"):
+    """cs = None: the interpreter's library"""
     with tempfile.TemporaryDirectory() as tmp:
-        header = os.path.join(tmp, "code.h")
-        open(header, "w").write(specialize.code_header(cs))
-        cmd = [specialize._hipcc(), *specialize.variant("exact")[1], f'-DRM_STATIC_CODE="{header}"']
-        if not specialize.static_backward(cs):
-            cmd.append("-DRM_NO_BACKWARD")
+        cmd = [specialize._hipcc(), *specialize.variant(precision)[1]]
+        if cs is not None:
+            header = os.path.join(tmp, "code.h")
+            open(header, "w").write(specialize.code_header(cs))
+            cmd.append(f'-DRM_STATIC_CODE="{header}"')
+            if not specialize.static_backward(cs):
+                cmd.append("-DRM_NO_BACKWARD")
         cmd.append(os.path.join(specialize.CSRC, "rm_abi.hip"))
         r = subprocess.run(cmd + ["-Rpass-analysis=kernel-resource-usage", "-o", os.path.join(tmp, "lib.so")],
                            capture_output=True, text=True, cwd=specialize.CSRC)
@@ -91,25 +97,30 @@ if __name__ == "__main__":
     asm_dir = sys.argv[sys.argv.index("--asm") + 1] if "--asm" in sys.argv else None
     if asm_dir:
         os.makedirs(asm_dir, exist_ok=True)
-    libs = {"scene2": R.make_test_scene2(), "closed1": R.make_closed_test_scene(), "many32": R.make_many_primitive_scene(32)}
+    every = "--all" in sys.argv
+    libs = {"scene2": R.make_test_scene2(), "closed1": R.make_closed_test_scene(), "many32": R.make_many_primitive_scene(32),
+            "generic": None, "fast": None}
     if "--only" in sys.argv:
         libs = {k: m for k, m in libs.items() if k in sys.argv[sys.argv.index("--only") + 1].split(",")}
-    compiled = {k: compile_scene(m) for k, m in libs.items()}
+    elif not every:
+        libs = {k: m for k, m in libs.items() if m is not None}
+    compiled = {k: compile_scene(m) if m is not None else None for k, m in libs.items()}
     with ThreadPoolExecutor(max_workers=3) as ex:
-        tables = dict(zip(libs, ex.map(lambda k: resources(compiled[k], asm_dir and os.path.join(asm_dir, k + ".s")), libs)))
+        tables = dict(zip(libs, ex.map(lambda k: resources(compiled[k], asm_dir and os.path.join(asm_dir, k + ".s"),
+                                                           "fast" if k == "fast" else "exact"), libs)))
     print(f"# flags {' '.join(specialize.variant('exact')[1])}")
     print(f"# {'library':8s} {'instr':>5s} {'kernel':34s} VGPR AGPR SGPR  spillS spillV scratch[B/lane]  occ[waves/SIMD]")
     for which in libs:
-        for kernel in sorted(k for k in tables[which] if k.startswith(KERNELS)):
+        for kernel in sorted(k for k in tables[which] if every or k.startswith(KERNELS)):
             k = tables[which][kernel]
-            print(f"{which:10s} {compiled[which].n_instr:5d} {kernel[:34]:34s} {k.get('VGPRs', '?'):>4s} {k.get('AGPRs', '?'):>4s} "
+            print(f"{which:10s} {compiled[which].n_instr if compiled[which] else 0:5d} {kernel[:34]:34s} {k.get('VGPRs', '?'):>4s} {k.get('AGPRs', '?'):>4s} "
                   f"{k.get('TotalSGPRs', '?'):>4s}  {k.get('SGPRs Spill', '?'):>6s} {k.get('VGPRs Spill', '?'):>6s} "
                   f"{k.get('ScratchSize [bytes/lane]', '?'):>15s}  {k.get('Occupancy [waves/SIMD]', '?'):>15s}")
     if asm_dir:
         print(f"# {'library':8s} {'kernel':34s}  VALU  SALU branch v_readlane v_mov  code[bytes]")
         for which in libs:
             counts = asm_counts(os.path.join(asm_dir, which + ".s"))
-            for kernel in sorted(k for k in counts if k.startswith(KERNELS)):
+            for kernel in sorted(k for k in counts if every or k.startswith(KERNELS)):
                 c = counts[kernel]
                 print(f"{which:10s} {kernel[:34]:34s} {c['valu']:5d} {c['salu']:5d} {c['branch']:6d} {c['readlane']:10d} {c['vmov']:5d}  "
                       f"{c['bytes']:11d}")

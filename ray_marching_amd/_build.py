@@ -16,11 +16,14 @@ LIBDIR = os.environ.get("RM_LIB_DIR") or os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIBDIR, "librm_hip.so")
 SOURCES = [os.path.join(CSRC, f) for f in ("rm_abi.hip", "rm_kernels.h", "rm_device.h", "rm_math.h")] + \
     [os.path.join(os.path.dirname(_HERE), "include", "rm_abi.h")]
-HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-shared", "-fPIC", "-std=c++17"]
+# -fno-slp-vectorize: the pairs the SLP vectoriser forms (v_pk_mul_f32, v_pk_add_f32) issue no faster than two scalar
+# instructions and need aligned register pairs: the scene-2 frame kernel drops from 96 to 83 VGPRs without them
+# ("The march step's issue cost")
+HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-shared", "-fPIC", "-std=c++17"]
 # opt-in "fast" arithmetic (RenderLoop(precision="fast")): 1-ulp v_sqrt_f32, reciprocal normalise, FMA
 # contraction.  Still fp32 throughout; no longer bit-identical with the reference's CPU op stream.
-HIPCC_FLAGS_FAST = ["--offload-arch=gfx950", "-O3", "-ffp-contract=fast", "-DRM_FAST_MATH", "-shared", "-fPIC",
-                    "-std=c++17"]
+HIPCC_FLAGS_FAST = ["--offload-arch=gfx950", "-O3", "-ffp-contract=fast", "-DRM_FAST_MATH", "-fno-slp-vectorize", "-shared",
+                    "-fPIC", "-std=c++17"]
 LIB_PATH_FAST = os.path.join(LIBDIR, "librm_hip_fast.so")
 
 

@@ -271,8 +271,11 @@ struct LdsParams {
 // of k_render_fwd served inference and recording frames, the SGPR form carried 997 v_readlane and VGPR copies won by 7 %
 // (238 -> 221 us; 127.5 -> 108.5 M executed VALU wave-instructions); once the inference instantiation was split off
 // (357 v_readlane) the SGPR form is the faster one: 0.205 ms against 0.215 ms with VGPR copies (round-2 tree on that box:
-// 0.208).  VGPR copies also cost 22 VGPRs per kernel: the ray pools got 29 % slower with them, the backward kernels
-// lose their last wave of occupancy.
+// 0.208).  What that last A/B compared is occupancy, not operand rate: VGPR copies of every float cost about 22 VGPRs per
+// kernel, which takes the scene-2 frame kernel from the 96-VGPR step to 4 waves per SIMD; the ray pools got 29 % slower
+// with them, the backward kernels lose their last wave of occupancy.  Copies of only the floats every step reads (9 for
+// scene 2) fit under the 96 once the SLP vectoriser is off, and were measured too: 0.8 % of the kernel, inside the
+// run-to-run spread, not adopted ("The march step's issue cost").
 template <int N, bool kVgpr = false>
 struct RegParams {
   float v[N > 0 ? N : 1];
@@ -589,9 +592,24 @@ RM_DEV void fwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
       // Inside the box every q <= 0, so relu(q) = (+0,+0,+0) and its norm is exactly +0: when that holds
       // for the whole wave (rays inside a room shell: always) the norm -- 3 max, mul, 2 fma and the
       // 9-instruction exact sqrt -- is skipped.  NaN fails (m <= 0) and takes the full path.
+      // On the skipped path the value 0 + (m < 0 ? m : 0) is m itself, bit for bit, so nothing is computed at all
+      // (it was v_mov, a canonicalising v_max, v_min and v_add on every step of every ray in a room): no lane has
+      // NaN; 0 + m = m for m < 0; and for m == 0 the old sum is +0 and so is m, because -0 cannot arise -- fabsf
+      // never gives -0, q = |p| - h is a round-to-nearest difference, which is +0 whenever it is zero (equal
+      // operands, h = -0 against |p| = +0 included), and a maximum of values none of which is -0 is not -0.
+      // RM_BOX_PLAIN: the expression as it was (A/B knob).
+#if defined(RM_BOX_PLAIN)
       float nr = 0.0f;
       if (!__all(m <= 0.0f)) nr = norm3_t<S::kFast>(mk3(t_relu_keep(qx), t_relu_keep(qy), t_relu_keep(qz)));
       s.d = nr + ((m < 0.0f) ? m : 0.0f);
+#else
+      if (__all(m <= 0.0f)) {
+        s.d = m;
+      } else {
+        float nr = norm3_t<S::kFast>(mk3(t_relu_keep(qx), t_relu_keep(qy), t_relu_keep(qz)));
+        s.d = nr + ((m < 0.0f) ? m : 0.0f);
+      }
+#endif
     } break;
     case RM_OP_PLANE:
       s.d = s.p.x;
