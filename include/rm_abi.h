@@ -118,7 +118,14 @@ enum {
                               the node's value is NAME_out_fwd(child value, p, theta), p in the node's own frame.  Like
                               RM_OP_USER both exist only in the per-scene specialised libraries: see rm_user_warps().  No bound is
                               known for the node (no cull test covers it; cull tests inside its child stay) */
-  RM_OP__COUNT = 24
+  RM_OP_MATERIAL = 24,     /* a material node (contrib.SDFMaterial), behind its child: the value passes through unchanged.  P: albedo[3]
+                              (read by the colour sweep only); aux0 = 1 marks an IMPLICIT material -- no parameters, `param offset` 0, the
+                              constant default colour (1, 1, 1) -- which the compiler puts behind every maximal subtree that no
+                              SDFMaterial covers, in scenes that hold at least one; aux1 = 0.  No tape slot, no stack.  The march, the
+                              taps, the bound walk and the geometry backward treat it as the identity; the colour sweep
+                              (rm_material_forward) adds |g| and |g| albedo there.  Like RM_OP_USER it exists only in the per-scene
+                              specialised libraries (built with RM_MATERIALS) */
+  RM_OP__COUNT = 25
 };
 #define RM_USER_COMB_MAX_CHILDREN 16
 
@@ -271,6 +278,18 @@ int rm_scene_bound(const RmScene* scene, float* out /*device [7]*/, void* stream
  * (nullable, OVERWRITTEN with the deterministic sum over rays). */
 int rm_sdf_backward(const RmScene* scene, const float* points, const float* grad_dist /*[n]*/,
                     float* grad_points, float* grad_params, float* partials, int64_t n, void* stream);
+
+/* Surface colour of a scene with material nodes (RM_OP_MATERIAL) at points: one recording evaluation and one reverse sweep with
+ * seed 1 per point, which does no leaf or parameter work.  With a_j = |d scene / d(value passing through material j)| by the
+ * rules of rm_sdf_backward (ties to the first child, culled children 0, user combinators and warp `out`s through their VJPs),
+ *   rgb = sum_j a_j albedo_j / sum_j a_j        ((1, 1, 1), the default colour, where sum_j a_j == 0).
+ * points, rgb: device fp32 [n,3].  rm_material_backward: grad_params[n_params] is OVERWRITTEN with the deterministic sum over
+ * the points of a_j / sum a . grad_rgb in the albedo floats and 0 everywhere else: the weights are constants, no gradient
+ * flows through them into shape parameters or points.  partials: rm_grad_partials_floats floats.  Both exist in the
+ * specialised libraries of scenes that hold material nodes; every other library answers RM_E_BADARG (nothing is launched). */
+int rm_material_forward(const RmScene* scene, const float* points, float* rgb, int64_t n, void* stream);
+int rm_material_backward(const RmScene* scene, const float* points, const float* grad_rgb /*[n,3]*/,
+                         float* grad_params, float* partials, int64_t n, void* stream);
 
 /* SDFMarcher.forward (rendering/ray_marching.py:72-84): p <- f(p)*v + p, `steps` times.
  * traj (nullable): device [steps,n,3], iterate p_i BEFORE step i (needed by backward).

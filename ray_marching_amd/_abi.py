@@ -32,6 +32,7 @@ OP_USER_END = 21      # the combinator itself: aux0 = first tape slot, aux1 = pa
 USER_COMB_MAX_CHILDREN = 16      # RM_USER_COMB_MAX_CHILDREN
 OP_USER_PUSH = 22     # enters a user-defined domain operator (extensions.register_warp): aux0 = warp type, aux1 = parameter floats
 OP_USER_POP = 23      # leaves it: aux0 = warp type, aux1 = parameter floats << 16 | (value slot + 1; 0 = the type has no `out`)
+OP_MATERIAL = 24      # a material node (contrib.SDFMaterial) behind its child: P = albedo[3]; aux0 = 1: implicit, no parameters, default colour
 
 FLAG_EARLY_OUT, FLAG_TILE8X8, FLAG_DYNAMIC_TILES, FLAG_REGEN, FLAG_ORDER_PER_RAY = 1, 2, 4, 8, 16
 ORDER_ONE_BLOCK, ORDER_SCRATCH_INTS = 131072, 8192
@@ -85,6 +86,8 @@ _SIGNATURES = {
     "rm_sdf_forward": (C.c_int, [C.POINTER(RmScene), _P, _P, C.c_int64, C.c_int32, _P]),
     "rm_scene_bound": (C.c_int, [C.POINTER(RmScene), _P, _P]),
     "rm_sdf_backward": (C.c_int, [C.POINTER(RmScene), _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "rm_material_forward": (C.c_int, [C.POINTER(RmScene), _P, _P, C.c_int64, _P]),
+    "rm_material_backward": (C.c_int, [C.POINTER(RmScene), _P, _P, _P, _P, C.c_int64, _P]),
     "rm_march_forward": (C.c_int, [C.POINTER(RmScene), _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
     "rm_march_backward": (C.c_int, [C.POINTER(RmScene), _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P]),
     "rm_normals_forward": (C.c_int, [C.POINTER(RmScene), C.POINTER(RmTetra), _P, _P, _P, C.c_int64, C.c_int32, _P]),

@@ -64,6 +64,8 @@ def _cost(node) -> int:
         return 25 + _cost(node.sdf)
     if kind in ("rounding", "onion"):
         return 1 + _cost(node.sdf)
+    if kind == "material":            # (the identity: no instruction of the march is spent on it)
+        return _cost(node.sdf)
     if kind == "union":
         return sum(_cost(c) + 1 for c in node.sdfs)
     if kind == "smooth_union":
@@ -84,11 +86,25 @@ def _boundable(node) -> bool:
         return spec.bounded
     if user == "warp":
         return spec.bounded and _boundable(warp_child(node, spec))
-    if kind in ("affine", "rounding", "onion"):
+    if kind in ("affine", "rounding", "onion", "material"):
         return _boundable(node.sdf)
     if kind in ("union", "smooth_union"):
         return all(_boundable(c) for c in node.sdfs)
     return False
+
+
+def _is_material(node) -> bool:
+    return getattr(node, "_rm_kind", None) == "material"
+
+
+def _has_material(node) -> bool:
+    """A material node (contrib.SDFMaterial) at or below this node."""
+    return any(_is_material(m) for m in node.modules())
+
+
+def _bare(node):
+    """The node with the material node around it, if any, taken off: what decides how its parent treats it."""
+    return node.sdf if _is_material(node) else node
 
 
 @dataclass
@@ -118,6 +134,9 @@ class CompiledScene:
     user_shader_normalise: object = None    # "minmax": its NAME_fwd returns a raw triple that NAME_finish maps through the frame's min / max
     user_shader_table: str = ""         # the attribute that holds its lookup table (register_shader(table=...)); "": none
     user_shader_table_taps: int = 0     # T: the most table rows one pixel's VJP contributes to; 0: no table
+    user_shader_material: bool = False  # its pair takes the surface colour of the material nodes (register_shader(material=True))
+    materials: int = 0                  # RM_OP_MATERIAL instructions, the implicit ones included (contrib.SDFMaterial); 0: none, the scene
+                                        # is what it always was.  > 0: the scene runs only through its specialised library (RM_MATERIALS)
     shader_offset: int = 0              # where its theta starts in the block (= the scene's own n_params)
     _device_programs: dict = field(default_factory=dict)
     _table: dict = field(default_factory=dict)
@@ -176,8 +195,15 @@ class CompiledScene:
 
     @property
     def has_user_types(self) -> bool:
-        """User-defined leaves, combinators or warps in the scene, or a user shader on it: no interpreter path (_user_leaf_lib)."""
-        return bool(self.user_leaves or self.user_combinators or self.user_warps or self.user_shader)
+        """User-defined leaves, combinators or warps in the scene, a user shader on it, or material nodes in it: no interpreter
+        path (_user_leaf_lib)."""
+        return bool(self.user_leaves or self.user_combinators or self.user_warps or self.user_shader or self.materials)
+
+    @property
+    def albedo_leaves(self):
+        """(index into ``leaves``, block offset) of the albedo of every SDFMaterial, in program order."""
+        at = {off: i for i, off in enumerate(self.leaf_offsets)}
+        return [(at[int(off)], int(off)) for op, off, a0, _ in self.program.tolist() if op == _abi.OP_MATERIAL and a0 == 0]
 
     @property
     def specialised(self) -> bool:
@@ -286,6 +312,11 @@ class _Emitter:
         # (default: also with the minimum of its children's own bounds, rm_device.h: cull_union_children)
         self.cull_union_table = os.environ.get("RM_CULL_UNION_TABLE", "1") != "0"
         self.want_table = False        # set by the parent union for the child it emits next
+        # material nodes (contrib.SDFMaterial): `cover` in a scene that holds one -- every leaf then ends up under exactly one
+        # RM_OP_MATERIAL, explicit or implicit -- and `covered` while the subtree of one is being emitted
+        self.cover = False
+        self.covered = False
+        self.materials = 0
         # the user types of each kind -> type index, in order of first appearance: (extensions.UserLeaf, parameter floats),
         # (extensions.UserCombinator, children, parameter floats), (extensions.UserWarp, parameter floats)
         self.user_types = {kind: {} for kind in _USER_TYPES}
@@ -328,7 +359,24 @@ def _emit(node, em: _Emitter, n_params: int):
     kind = getattr(node, "_rm_kind", None)
     spec, user = _user(node)
     A = _abi
-    if kind == "sphere":
+    if em.cover and not em.covered and kind != "material" and not _has_material(node):
+        # a maximal subtree with no material node above or inside it: the implicit material, default colour, no parameters
+        # (em.want_table stays as the parent set it: the subtree is emitted as it always was)
+        em.covered = True
+        _emit(node, em, n_params)
+        em.covered = False
+        em.ins(A.OP_MATERIAL, 0, 1, 0)
+        em.materials += 1
+        return
+    if kind == "material":
+        if em.covered:
+            raise ValueError("an SDFMaterial inside the subtree of another SDFMaterial: every leaf has exactly one material")
+        em.covered = True
+        _emit(node.sdf, em, n_params)
+        em.covered = False
+        em.ins(A.OP_MATERIAL, em.off(node.albedo), 0, 0)
+        em.materials += 1
+    elif kind == "sphere":
         em.ins(A.OP_SPHERE, em.off(node.radius))
     elif kind == "box":
         em.ins(A.OP_BOX, em.off(node.halfsides))
@@ -400,7 +448,7 @@ def _emit(node, em: _Emitter, n_params: int):
             if cull_children:
                 lse_at = len(em.code)
                 em.ins(A.OP_CULL_LSE, lse_table + 8 * i, base + i, 0)           # aux1 patched below
-            if cull_at is not None and em.cull_union_table and getattr(child, "_rm_kind", None) == "smooth_union":
+            if cull_at is not None and em.cull_union_table and getattr(_bare(child), "_rm_kind", None) == "smooth_union":
                 em.want_table = True           # the child emits a bound table on its SMOOTH_BEGIN when its slots allow
             _emit(child, em, n_params)
             em.want_table = False
@@ -487,7 +535,7 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
         table[id(p)] = cursor
         cursor += p.numel()
     shader_offset, user_shader, shader_source, shader_probes, shader_chained, shader_normalise = cursor, (), "", 0, False, None
-    shader_table, shader_table_taps = "", 0
+    shader_table, shader_table_taps, shader_material = "", 0, False
     if shader is not None:
         spec = shader_spec(shader)
         if spec is None:
@@ -501,11 +549,12 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
             cursor += p.numel()
         user_shader, shader_source, shader_probes = (spec.name, cursor - shader_offset, spec.sha1), spec.hip, spec.probes
         shader_chained, shader_normalise = spec.chained, spec.normalise
-        shader_table, shader_table_taps = spec.table, spec.table_taps
+        shader_table, shader_table_taps, shader_material = spec.table, spec.table_taps, spec.material
     n_params = cursor                 # (derived constants start behind the shader's floats)
     em = _Emitter(table)
     # derived block = [capsule constants of every SDFLine (gradients flow through them) | cull bounds, bound tables]
     em.n_grad_derived = em.n_derived = 6 * sum(1 for m in module.modules() if getattr(m, "_rm_kind", None) == "line")
+    em.cover = _has_material(module)
     _emit(module, em, n_params)
     if em.next_line != em.n_grad_derived:
         raise ValueError("an SDF node instance appears more than once in the scene tree (shared sub-modules are not supported)")
@@ -530,6 +579,8 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
         slots.append(("normalise", shader_normalise))
     if shader_table:                  # (... and one that reads a lookup table: its pair takes tab / gt.  L and the values stay run-time)
         slots.append(("table", shader_table, shader_table_taps))
+    if shader_material:               # (... and one that reads the surface colour: its pair takes m / gm)
+        slots.append(("material",))
     signature = (tuple(map(tuple, program.tolist())), n_params, em.n_derived, em.max_depth, em.n_slots, em.n_grad_derived, *slots)
     return CompiledScene(program=program, leaves=leaves, leaf_names=names, leaf_offsets=offsets,
                          n_params=n_params, n_derived=em.n_derived, n_grad_derived=em.n_grad_derived, stack_floats=em.max_depth,
@@ -542,7 +593,8 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
                          user_shader=user_shader, user_shader_source=shader_source, shader_offset=shader_offset,
                          user_shader_probes=shader_probes, user_shader_chained=shader_chained,
                          user_shader_normalise=shader_normalise, user_shader_table=shader_table,
-                         user_shader_table_taps=shader_table_taps)
+                         user_shader_table_taps=shader_table_taps, materials=em.materials,
+                         user_shader_material=shader_material)
 
 
 def structure_key(module: nn.Module):

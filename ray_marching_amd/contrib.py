@@ -459,6 +459,80 @@ def make_warped_scene(bounded: bool = False):
 
 
 # --------------------------------------------------------------------------------------------------------------------
+# Material nodes: a colour per object (extensions.py: "material nodes")
+# --------------------------------------------------------------------------------------------------------------------
+from .scene._base import SDFCoordsNode  # noqa: E402
+
+
+class SDFMaterial(SDFCoordsNode):
+    """The child, unchanged, carrying a surface colour: ``SDFMaterial(x)(points) == x(points)`` bit for bit.  ``albedo`` [3] is
+    a float32 parameter that no distance depends on; ``surface_albedo`` reads it.  A material node may not sit inside the
+    subtree of another one, and in a scene that holds one every subtree no material covers gets the default colour (1, 1, 1)."""
+    _rm_kind = "material"
+
+    def __init__(self, sdf: nn.Module, albedo=(1.0, 1.0, 1.0)) -> None:
+        super().__init__()
+        self.albedo = nn.Parameter(torch.tensor(albedo, dtype=torch.float32))
+        self.sdf = sdf
+        if self.albedo.shape != (3,):
+            raise ValueError(f"SDFMaterial: albedo is (r, g, b), not a tensor of shape {tuple(self.albedo.shape)}")
+
+    def forward(self, query_coords: Tensor) -> Tensor:
+        # (CPU points: the child's own forward, where it has one -- the material is the identity)
+        return self._evaluate(query_coords) if query_coords.is_cuda else self.sdf(query_coords)
+
+
+def strip_materials(scene: nn.Module) -> nn.Module:
+    """A deep copy of ``scene`` with every SDFMaterial replaced by its child: the geometry alone."""
+    import copy
+    scene = copy.deepcopy(scene)
+
+    def strip(node):
+        while isinstance(node, SDFMaterial):
+            node = node.sdf
+        for name, child in list(node._modules.items()):
+            if child is not None:
+                node._modules[name] = strip(child)
+        return node
+
+    return strip(scene)
+
+
+def surface_albedo(scene: nn.Module, points: Tensor) -> Tensor:
+    """The surface colour ``m(p) = sum_j a_j c_j / sum_j a_j`` of a scene with material nodes at ``points[..., 3]`` -> ``[..., 3]``
+    (float32, on the scene's ROCm device): ``c_j`` the albedo of material ``j`` and ``a_j = |d scene / d(value passing through
+    material j)|`` by the rules of the scene's own backward pass -- the winner of a union, the softmax weights of a smooth
+    union, whatever a user combinator's VJP says; (1, 1, 1) where the sum is 0.  Differentiable with respect to the albedos
+    only: the weights are constants, so the points and the shape parameters receive no gradient (None)."""
+    from . import ops
+    from .compiler import compiled_for
+    cs = compiled_for(scene)
+    if not cs.materials:
+        raise ValueError("surface_albedo: the scene holds no SDFMaterial")
+    if points.shape[-1] != 3:
+        raise ValueError(f"points must be [..., 3], got {tuple(points.shape)}")
+    return ops.SurfaceAlbedo.apply(points, cs, *(cs.leaves[i] for i, _ in cs.albedo_leaves))
+
+
+def make_painted_scene():
+    """The room of make_test_scene2() around a smooth union (``blend_k = 8``) of that scene's sphere, moved by (0.3, 0.2, 0), its
+    torus and its capsule, each under a material of its own, and one on the room: red sphere, green torus, blue capsule, grey
+    walls, blending where the smooth union blends."""
+    from .scene.primitives import SDFLine, SDFSphere, SDFTorus
+    from .scene.scene_registry import make_room
+    from .scene.transformations import SDFAffineTransformation, SDFSmoothUnion, SDFUnion
+    return SDFUnion([
+        SDFMaterial(make_room(), albedo=(0.7, 0.7, 0.7)),
+        SDFSmoothUnion(sdfs=[
+            SDFMaterial(SDFAffineTransformation(SDFSphere(radius=0.5), orientation=[1.0, 0.0, 0.0, 0.0], translation=[0.3, 0.2, 0.0]),
+                        albedo=(0.9, 0.2, 0.2)),
+            SDFMaterial(SDFTorus(radius1=1.0, radius2=0.25), albedo=(0.2, 0.8, 0.3)),
+            SDFMaterial(SDFLine(start=(1.0, 0.0, 0.0), end=(-1.0, 0.0, 0.0), radius=0.1), albedo=(0.2, 0.3, 0.9)),
+        ], blend_k=8.0),
+    ])
+
+
+# --------------------------------------------------------------------------------------------------------------------
 # Per-pixel shaders (extensions.register_shader): what lights a user's solid, with parameters of its own to optimise
 # --------------------------------------------------------------------------------------------------------------------
 class DirectionalLightShader(nn.Module):
@@ -1140,3 +1214,44 @@ template <bool Fast> RM_DEV void depth_palette_vjp(const rm::ShadeIn& s, const f
 """
 
 register_shader(DepthPaletteShader, params=("density",), hip=_DEPTH_PALETTE_HIP, table="palette", table_taps=2)
+
+
+class MaterialLambertShader(nn.Module):
+    """The Lambertian term on the surface colour of the scene's material nodes (SDFMaterial): ``rgb = m * (ambient + (1 - ambient)
+    * clamp(-(v . n), 0, 1))``.  One parameter float (``ambient``); reads the direction, the normal and the material colour ``m``,
+    which is (1, 1, 1) on a scene without material nodes."""
+
+    def __init__(self, ambient: float = 0.1) -> None:
+        super().__init__()
+        self.ambient = nn.Parameter(torch.tensor(ambient, dtype=torch.float32))
+
+    def forward(self, px_coords: Tensor, camera_orientation: Tensor, pixel_frames: Tensor, ray_directions: Tensor,
+                surface_coords: Tensor, surface_normals: Tensor, material: Tensor) -> Tensor:
+        c = (ray_directions * surface_normals).sum(dim=-1, keepdim=True).neg().clamp(0, 1)
+        return material * (self.ambient + (1 - self.ambient) * c)
+
+
+# theta = {ambient}; the forward restates the ATen op stream above (mul().sum(-1): dot_seq, neg, clamp: t_clamp, every product and
+# sum rounded on its own), the VJP is autograd's, written out; gm = dL/dm
+_MATERIAL_LAMBERT_HIP = r"""
+template <bool Fast> RM_DEV rm::V3 material_lambert_fwd(const rm::ShadeIn& s, const float* theta, rm::V3 m) {
+  const float c = t_clamp(-dot_seq(s.v, s.n), 0.0f, 1.0f);
+  const float k = theta[0] + (1.0f - theta[0]) * c;
+  return mk3(m.x * k, m.y * k, m.z * k);
+}
+template <bool Fast> RM_DEV void material_lambert_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 m, rm::V3 g, rm::ShadeGrad& gs,
+                                                      float* gtheta, rm::V3& gm) {
+  const float d = -dot_seq(s.v, s.n);
+  const float c = t_clamp(d, 0.0f, 1.0f);
+  const float k = theta[0] + (1.0f - theta[0]) * c;
+  gm = mk3(g.x * k, g.y * k, g.z * k);
+  const float gk = (g.x * m.x + g.y * m.y) + g.z * m.z;
+  gtheta[0] = gk - gk * c;
+  const float gc = gk * (1.0f - theta[0]);
+  const float gd = (d >= 0.0f && d <= 1.0f) ? gc : 0.0f;       // clamp passes the gradient on the closed interval
+  gs.n = gs.n + mk3(-gd * s.v.x, -gd * s.v.y, -gd * s.v.z);
+  gs.v = gs.v + mk3(-gd * s.n.x, -gd * s.n.y, -gd * s.n.z);
+}
+"""
+
+register_shader(MaterialLambertShader, params=("ambient",), hip=_MATERIAL_LAMBERT_HIP, material=True)

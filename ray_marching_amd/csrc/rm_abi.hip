@@ -275,6 +275,44 @@ int rm_sdf_backward(const RmScene* scene, const float* points, const float* grad
 #endif
 }
 
+int rm_material_forward(const RmScene* scene, const float* points, float* rgb, int64_t n, void* stream) {
+#ifndef RM_MATERIALS
+  (void)scene; (void)points; (void)rgb; (void)n; (void)stream;
+  return fail(RM_E_BADARG, "rm_material_forward: this library was built without material nodes (only the specialised library of "
+                           "a scene that holds an SDFMaterial has the colour sweep)");
+#else
+  if (int e = check_scene(scene)) return e;
+  if (n < 0 || (n > 0 && (!points || !rgb))) return fail(RM_E_BADARG, "rm_material_forward: null buffer");
+  if (n == 0) return RM_OK;
+  Launch L;
+  if (int e = pick_launch(rm::k_material_fwd<G>, *scene, false, 256, &L)) return e;
+  int grid = grid_for((n + L.block - 1) / L.block, kMaxBlocks);
+  rm::k_material_fwd<G><<<grid, L.block, L.lds, (hipStream_t)stream>>>(*scene, points, rgb, n);
+  return launched("k_material_fwd");
+#endif
+}
+
+int rm_material_backward(const RmScene* scene, const float* points, const float* grad_rgb, float* grad_params,
+                         float* partials, int64_t n, void* stream) {
+#if !defined(RM_MATERIALS)
+  (void)scene; (void)points; (void)grad_rgb; (void)grad_params; (void)partials; (void)n; (void)stream;
+  return fail(RM_E_BADARG, "rm_material_backward: this library was built without material nodes (only the specialised library "
+                           "of a scene that holds an SDFMaterial has the colour sweep)");
+#elif defined(RM_NO_BACKWARD)
+  (void)scene; (void)points; (void)grad_rgb; (void)grad_params; (void)partials; (void)n; (void)stream;
+  return fail(RM_E_BADARG, "rm_material_backward: this specialised library was built forward-only");
+#else
+  if (int e = check_scene(scene)) return e;
+  if (n <= 0 || !points || !grad_rgb || !partials) return fail(RM_E_BADARG, "rm_material_backward: null buffer / n<=0");
+  Launch L;
+  if (int e = pick_launch(rm::k_material_bwd<GB>, *scene, true, 128, &L)) return e;
+  int grid = grid_for((n + L.block - 1) / L.block, 1024);
+  rm::k_material_bwd<GB><<<grid, L.block, L.lds, (hipStream_t)stream>>>(*scene, points, grad_rgb, partials, n);
+  if (int e = launched("k_material_bwd")) return e;
+  return reduce_partials(*scene, partials, grid, grad_params, (hipStream_t)stream);
+#endif
+}
+
 int rm_march_forward(const RmScene* scene, const void* pos, const void* dirs, void* out_pos, float* traj,
                      int32_t* nexec, int64_t n, int32_t steps, int32_t flags, int32_t dtype, void* stream) {
   if (int e = check_scene(scene)) return e;
@@ -831,7 +869,7 @@ int rm_sum_rows(const float* rows, int64_t n_rows, int32_t width, float* out, vo
 int rm_validate_program(const int32_t* host_program, int32_t n_instr, int32_t n_params, int32_t n_derived,
                         int32_t stack_floats, int32_t n_slots) {
   if (!host_program || n_instr <= 0) return fail(RM_E_PROGRAM, "empty program");
-  static const int psize[RM_OP__COUNT] = {0, 1, 3, 0, 7, 1, 2, 7, 7, 0, 0, 0, 0, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+  static const int psize[RM_OP__COUNT] = {0, 1, 3, 0, 7, 1, 2, 7, 7, 0, 0, 0, 0, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0};
   int depth_f = 0, depth_b = 0, max_f = 0, max_b = 0, values = 0;
   for (int i = 0; i < n_instr; ++i) {
     const int32_t* w = host_program + 4 * i;
@@ -902,6 +940,11 @@ int rm_validate_program(const int32_t* host_program, int32_t n_instr, int32_t n_
                       i, off, a0, np, j, v[1], v[2], v[3]);
         depth_f -= 3; depth_b -= 6;
       } break;
+      case RM_OP_MATERIAL:    // behind its child: the value passes through.  aux0 = 1: implicit (no parameters), else P: albedo[3]
+        if ((a0 != 0 && a0 != 1) || a1 != 0 || (a0 == 1 && off != 0) || (a0 == 0 && (off < 0 || off + 3 > n_params)))
+          return fail(RM_E_PROGRAM, "instr %d: MATERIAL albedo out of range", i);
+        if (values != 1) return fail(RM_E_PROGRAM, "instr %d: MATERIAL without a value in front of it", i);
+        break;
       case RM_OP_AFFINE_PUSH: depth_f += 3; depth_b += 6; break;
       case RM_OP_AFFINE_POP: depth_f -= 3; depth_b -= 6; break;
       case RM_OP_UNION_BEGIN: depth_f += 1; depth_b += 2; break;

@@ -756,10 +756,21 @@ RM_DEV void smooth_end_static(S& s, const PT& P, int off) {
 // Gradient accumulators live in the store at index acc0 + parameter offset
 // (raw parameters first, derived constants after them).
 // --------------------------------------------------------------------------
-template <class Store, bool Acc = true, bool Fast = (RM_FAST_VJP != 0)>
+// Material sweeps (RM_OP_MATERIAL; libraries built with RM_MATERIALS): the same walk with Mat != 0 does no leaf and no parameter
+// work -- only how `g` travels from the root to every material node matters.  kMatColour: each material adds |g| to `ma` and
+// |g| albedo to `mc` (the surface colour is mc / ma).  kMatGrad: each material adds |g| mg into its albedo's accumulators, mg =
+// dL/d(colour) / ma.  Both run behind a recording forward and leave the tape as they found it, like every reverse pass.
+constexpr int kMatColour = 1, kMatGrad = 2;
+template <class Store, bool Acc = true, bool Fast = (RM_FAST_VJP != 0), int Mat = 0>
 struct Bwd {
   static constexpr bool kAcc = Acc;   // false: point gradient only (no parameter accumulators are touched)
   static constexpr bool kFast = Fast; // 1-ulp square roots and reciprocals (sqrt_t, div_t)
+  static constexpr int kMat = Mat;
+#ifdef RM_MATERIALS
+  float ma;      // kMatColour: sum of the weights |g| met so far
+  V3 mc;         // kMatColour: sum of |g| albedo
+  V3 mg;         // kMatGrad: dL/d(colour) / sum of the weights
+#endif
   V3 p;
   V3 gp;
   float g;
@@ -788,7 +799,26 @@ RM_DEV V3 safe_unit_scaled(V3 w, float n, float g) {
 template <class S, class PT>
 RM_DEV void bwd_op(S& s, const PT& P, int op, int off, int a0, int a1) {
   const int A = s.acc0;
+#ifdef RM_MATERIALS
+  if constexpr (S::kMat != 0) {   // a material sweep: `g` ends at the leaves, nothing is asked of them
+    if (op == RM_OP_SPHERE || op == RM_OP_BOX || op == RM_OP_PLANE || op == RM_OP_LINE || op == RM_OP_DISK || op == RM_OP_TORUS ||
+        op == RM_OP_USER)
+      return;
+  }
+#endif
   switch (op) {
+#ifdef RM_MATERIALS
+    case RM_OP_MATERIAL: {  // a0 = 1: the implicit material, no parameters, the default colour.  `g` passes through.
+      const float a = fabsf(s.g);
+      if constexpr (S::kMat == kMatColour) {
+        const V3 c = (a0 != 0) ? mk3(1.0f, 1.0f, 1.0f) : P.v3(off);
+        s.ma = s.ma + a;
+        s.mc = s.mc + a * c;
+      } else if constexpr (S::kMat == kMatGrad) {
+        if (a0 == 0) { s.st->add(A + off, a * s.mg.x); s.st->add(A + off + 1, a * s.mg.y); s.st->add(A + off + 2, a * s.mg.z); }
+      }
+    } break;
+#endif
     case RM_OP_SPHERE: {
       float n = norm3_t<S::kFast>(s.p);
       s.gp = s.gp + safe_unit_scaled<S>(s.p, n, s.g);
@@ -1197,6 +1227,29 @@ struct Scene {
   // anchor, the recursion, then the parameter pass with the summed upstream.
   mutable unsigned long long last_culled = 0ull;   // skip bits of the last recording forward
   RM_DEV V3 vjp_replay(V3 p, float g) const { return reverse<true>(p, g); }
+#ifdef RM_MATERIALS
+  // The surface colour at the point of the LAST record_fwd of this context (no scene evaluation in between): one reverse sweep
+  // with seed 1.  m = sum_j a_j albedo_j / sum_j a_j with a_j = |g| at material j, the default colour (1, 1, 1) where the sum is
+  // 0; `sum` (optional) receives sum_j a_j.  The tape is left as it was, so material_grads may follow without a second forward.
+  RM_DEV V3 material_colour(V3 p, float* sum = nullptr) const {
+    Bwd<Store, false, (RM_FAST_VJP != 0), kMatColour> b;
+    b.p = p; b.gp = mk3(0.0f, 0.0f, 0.0f); b.g = 1.0f; b.gframe = 0.0f; b.fval = 0.0f;
+    b.sp = 0; b.tape0 = tape0; b.acc0 = acc0; b.st = st; b.culled = last_culled;
+    b.ma = 0.0f; b.mc = mk3(0.0f, 0.0f, 0.0f); b.mg = mk3(0.0f, 0.0f, 0.0f);
+    prog.backward(b, P);
+    if (sum) *sum = b.ma;
+    return (b.ma == 0.0f) ? mk3(1.0f, 1.0f, 1.0f) : mk3(b.mc.x / b.ma, b.mc.y / b.ma, b.mc.z / b.ma);
+  }
+  // ... and its VJP with respect to the albedos: a second sweep over the same tape adds a_j mg into the accumulators of albedo
+  // j, mg = dL/dm / sum_j a_j (zero where the sum is 0: the default colour has no gradient).  The weights are constants.
+  RM_DEV void material_grads(V3 p, V3 mg) const {
+    Bwd<Store, false, (RM_FAST_VJP != 0), kMatGrad> b;
+    b.p = p; b.gp = mk3(0.0f, 0.0f, 0.0f); b.g = 1.0f; b.gframe = 0.0f; b.fval = 0.0f;
+    b.sp = 0; b.tape0 = tape0; b.acc0 = acc0; b.st = st; b.culled = last_culled;
+    b.ma = 0.0f; b.mc = mk3(0.0f, 0.0f, 0.0f); b.mg = mg;
+    prog.backward(b, P);
+  }
+#endif
 };
 
 // --------------------------------------------------------------------------
@@ -1379,7 +1432,7 @@ RM_DEV void subtree_bound(GetIns ins, const float* P, int begin, int end, float*
       case RM_OP_USER_POP: --sp; cx = cy = cz = 0.0f; R = Ru = inf; slope = uslope = 1.0f; break;
 #endif
 #endif
-      default: break;            // nested CULL_MIN / CULL_LSE: no effect on the bound
+      default: break;            // nested CULL_MIN / CULL_LSE, RM_OP_MATERIAL (the identity): no effect on the bound
     }
   }
   if (overflow || !(R == R) || !(slope > 0.5f)) R = inf;

@@ -226,6 +226,49 @@ __global__ void __launch_bounds__(256) k_sdf_bwd(RmScene sc, const float* __rest
   flush_accumulators<Cfg>(scene, n_acc, partials, rm_smem + ((sc.n_params + sc.n_derived + 3) & ~3));
 }
 
+// Surface colour of a scene with material nodes at points (rm_material_forward / rm_material_backward): the launch shape of
+// k_sdf_fwd / k_sdf_bwd, one recording evaluation and one (backward: two) material sweeps per point over the same tape.
+#ifdef RM_MATERIALS
+template <class Cfg>
+__global__ void __launch_bounds__(256) k_material_fwd(RmScene sc, const float* __restrict__ pts, float* __restrict__ rgb, int64_t n) {
+  typename Cfg::Store store;
+  auto scene = Cfg::setup(sc, rm_smem, store);
+  int64_t ntiles = (n + blockDim.x - 1) / blockDim.x;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    int64_t i = tile * blockDim.x + threadIdx.x;
+    bool live = i < n;
+    int64_t ic = live ? i : n - 1;
+    const V3 p = load3(pts, ic);
+    scene.record_fwd(p, nullptr);
+    const V3 m = scene.material_colour(p);
+    if (live) store3(rgb, i, m);
+  }
+}
+
+template <class Cfg>
+__global__ void __launch_bounds__(256) k_material_bwd(RmScene sc, const float* __restrict__ pts, const float* __restrict__ grgb,
+                               float* __restrict__ partials, int64_t n) {
+  typename Cfg::Store store;
+  auto scene = Cfg::setup(sc, rm_smem, store, true);
+  const int n_acc = Cfg::n_acc(sc);
+  zero_accumulators<Cfg>(scene, n_acc);
+  int64_t ntiles = (n + blockDim.x - 1) / blockDim.x;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    int64_t i = tile * blockDim.x + threadIdx.x;
+    bool live = i < n;
+    int64_t ic = live ? i : n - 1;
+    const V3 p = load3(pts, ic);
+    const V3 gm = live ? load3(grgb, ic) : mk3(0.0f, 0.0f, 0.0f);
+    scene.record_fwd(p, nullptr);
+    float sum;
+    (void)scene.material_colour(p, &sum);
+    const float inv = (sum == 0.0f) ? 0.0f : 1.0f / sum;
+    scene.material_grads(p, mk3(gm.x * inv, gm.y * inv, gm.z * inv));
+  }
+  flush_accumulators<Cfg>(scene, n_acc, partials, rm_smem + ((sc.n_params + sc.n_derived + 3) & ~3));
+}
+#endif
+
 // Bounding sphere of the whole scene (rm_scene_bound): one block stages the scene as every kernel does, then one lane
 // walks the whole program with the walk that fills the cull tests' bounds.
 template <class Cfg>
@@ -1132,6 +1175,17 @@ struct UserShader {
   float d[RM_USER_SHADER_PROBES] = {};
   template <class SceneT> RM_DEV void probe(const SceneT& scene, const ShadeIn& si) { user_probe_values(scene, si, theta.v, d); }   // in front of fwd
   RM_DEV V3 fwd(const ShadeIn& si) const { return user_shader_fwd<false>(si, theta.v, d); }
+#elif defined(RM_USER_SHADER_MATERIAL)
+  // a shader that reads the surface colour (register_shader(material=True)): one recording evaluation at the hit point and one
+  // material sweep (Scene::material_colour), in the place of the probes; the default colour where the scene has no material nodes
+  V3 m = {1.0f, 1.0f, 1.0f};
+  template <class SceneT> RM_DEV void probe([[maybe_unused]] const SceneT& scene, [[maybe_unused]] const ShadeIn& si) {
+#ifdef RM_MATERIALS
+    scene.record_fwd(si.p, nullptr);
+    m = scene.material_colour(si.p);
+#endif
+  }
+  RM_DEV V3 fwd(const ShadeIn& si) const { return user_shader_fwd<false>(si, theta.v, m); }
 #else
   template <class SceneT> RM_DEV void probe(const SceneT&, const ShadeIn&) {}
 #ifdef RM_USER_SHADER_TABLE
@@ -2450,6 +2504,21 @@ __global__ void __launch_bounds__(256) RM_BWD_OCC k_render_bwd(RenderArgs a) {
         const V3 gq = scene.vjp(user_shader_probe<false>(k, si, theta), live ? gk : 0.0f);
         user_shader_probe_vjp<(RM_FAST_VJP != 0)>(k, si, theta, gq, gs, gtheta);
       }
+#endif
+#elif defined(RM_USER_SHADER_MATERIAL)
+      // a shader that reads the surface colour: m again (one recording evaluation, one material sweep), the shader's VJP, which also
+      // hands back gm = dL/dm, then a second sweep over the same tape that adds a_j / sum a . gm into the accumulators of albedo j.
+      // No scene evaluation lies between the forward and the two sweeps; every lane reaches them (the rows sum over the wave).
+      V3 m = mk3(1.0f, 1.0f, 1.0f), gm = z3;
+#ifdef RM_MATERIALS
+      float msum = 0.0f;
+      scene.record_fwd(p, nullptr);
+      m = scene.material_colour(p, &msum);
+#endif
+      user_shader_vjp<(RM_FAST_VJP != 0)>(si, theta, m, gi3, gs, gtheta, gm);
+#ifdef RM_MATERIALS
+      const float minv = 1.0f / msum;
+      scene.material_grads(p, (live && msum != 0.0f) ? mk3(gm.x * minv, gm.y * minv, gm.z * minv) : z3);
 #endif
 #elif defined(RM_USER_SHADER_TABLE)
       // a shader with a lookup table: its VJP also hands back up to T (row, dL/d(row)) pairs.  Where the table wants a gradient

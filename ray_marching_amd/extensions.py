@@ -159,6 +159,34 @@ the pixel's index: two backwards give the same bits.  A buffer table (or ``requi
 ``forward`` needs nothing new: it indexes ``self.ATTR``.  ``table=`` together with ``probes`` or ``normalise=`` is refused at registration
 (not built yet).
 
+*Material nodes* give every object a colour of its own: ``contrib.SDFMaterial(sdf, albedo=(r, g, b))`` is a unary scene node whose
+value is its child's, unchanged, and whose ``albedo`` no distance depends on.  The scene's value at ``p`` is ``f(p)``; with ``a_j =
+|df / d(value passing through material j)|`` -- computed by exactly the rules of the scene's reverse pass: the winner of a union
+(ties to the first child), the softmax weights of a smooth union, 0 for a culled child, whatever a user combinator's ``NAME_vjp`` or
+a warp's ``NAME_out_vjp`` says -- the surface colour is
+
+    m(p) = sum_j a_j c_j / sum_j a_j        (the default colour (1, 1, 1) where sum_j a_j == 0).
+
+Under unions, smooth unions, rounding, onion and affine nodes ``sum_j a_j`` is 1 up to rounding; dividing by it keeps ``m`` a convex
+blend under a scaling warp or a subtraction as well, and the surface cut by ``contrib.SDFSubtraction`` takes the cutter's colour.
+A material node may not sit inside another one's subtree (``ValueError`` at compile time), and in a scene that holds at least one,
+every maximal subtree without a material node above or inside it is covered by an implicit material of the default colour, so that
+every leaf is under exactly one.  The weights are treated as CONSTANTS: gradients reach the albedos, because ``m`` is linear in
+them, and the geometry through ``p`` and ``n`` as before; no gradient flows through ``a_j`` into shape parameters or into ``p`` (that
+needs second derivatives of the scene), and PyTorch references detach the weights.  ``contrib.surface_albedo(scene, points)`` is
+``m`` at chosen points.  A shader reads it with ``register_shader(..., material=True)``; the pair becomes
+
+    template <bool Fast> RM_DEV rm::V3 NAME_fwd(const rm::ShadeIn& s, const float* theta, rm::V3 m);
+    template <bool Fast> RM_DEV void   NAME_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 m, rm::V3 g, rm::ShadeGrad& gs,
+                                                float* gtheta, rm::V3& gm);
+
+``gm = dL/dm`` arrives zeroed; the kernels add ``a_j / sum a * gm`` into the albedos' accumulators in a fixed order (two backwards
+give the same bits).  The PyTorch ``forward`` takes one more trailing argument, ``material[..., 3]``.  On a scene without material
+nodes ``m`` is the default colour, no sweep is compiled and there are no albedos.  A scene with material nodes rendered with a
+built-in mode, or with a shader registered without ``material=True``, renders bit-identically to the same scene with the nodes
+stripped, and its albedos get zero gradients.  ``material=True`` together with ``probes``, ``normalise=`` or ``table=`` is refused at
+registration (not built yet).  Scenes with material nodes run only through their specialised library, like user nodes.
+
 Scenes that contain such a leaf, combinator or warp, and frames shaded by such a shader, run only through their per-scene specialised library (specialize.py), into which
 the source is compiled; the LDS interpreter has no handler for them and ``CompiledScene.lib()`` says so instead of
 rendering a wrong picture.
@@ -221,6 +249,7 @@ class UserShader(_UserSpec):
     normalise: object = None    # "minmax": NAME_fwd returns the raw triple, NAME_finish / NAME_finish_vjp map it through the frame's min / max
     table: str = ""     # attribute that holds the lookup table ([L, 3] float32 buffer or nn.Parameter; the pair takes tab / gt); "": none
     table_taps: int = 0     # T: the most table rows one pixel's VJP contributes to (1..RM_USER_SHADER_MAX_TABLE_TAPS); 0: no table
+    material: bool = False  # the pair takes the surface colour of the scene's material nodes, `rm::V3 m` (and the VJP `rm::V3& gm`)
 
 
 @dataclass(frozen=True)
@@ -267,7 +296,7 @@ _KINDS = {
         "`template <bool Fast> RM_DEV void NAME_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 g, rm::ShadeGrad& gs, float* "
         "gtheta)`",
         methods=(("forward", "forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals)"),),
-        same=("sha1", "params", "probes", "chained", "normalise", "table", "table_taps"), device_forward=False, probe_pair=True, finish_pair=True),
+        same=("sha1", "params", "probes", "chained", "normalise", "table", "table_taps", "material"), device_forward=False, probe_pair=True, finish_pair=True),
 }
 
 NORMALISATIONS = (None, "minmax")    # register_shader(normalise=...): the frame statistics a shader may be normalised by
@@ -333,6 +362,18 @@ def _table_arguments(hip: str, name: str):
 
     return (re.search(r"\bTable\s*&", arguments("fwd")) is not None and re.search(r"\bTable\s*&", arguments("vjp")) is not None,
             re.search(r"\bTableGrad\s*&", arguments("vjp")) is not None)
+
+
+def _material_arguments(hip: str, name: str):
+    """(NAME_fwd and NAME_vjp take a ``rm::V3 m``, NAME_vjp takes a ``rm::V3& gm``): read from the two parameter lists of the source."""
+    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
+
+    def arguments(fn):
+        m = re.search(r"\b%s_%s\s*\(([^)]*)\)" % (re.escape(name), fn), text)
+        return m.group(1) if m else ""
+
+    return (re.search(r"\bV3\s+m\b", arguments("fwd")) is not None and re.search(r"\bV3\s+m\b", arguments("vjp")) is not None,
+            re.search(r"\bV3\s*&\s*gm\b", arguments("vjp")) is not None)
 
 
 def _has_bound(text: str, name: str, what: str) -> bool:
@@ -430,6 +471,13 @@ def _register(kind: str, cls, *, params, hip: str, **own):
             raise ValueError(f"{fn}: the source of {cls.__name__} defines {name}_finish / {name}_finish_vjp, but normalise=None")
         if normalise is not None and not has_finish:
             raise ValueError(f"{fn}: normalise={normalise!r}, but the source of {cls.__name__} defines no {name}_finish / {name}_finish_vjp")
+    if "material" in own:      # (before the table's own checks: the combination is what is refused, whatever the source looks like)
+        material = own["material"]
+        if not isinstance(material, bool):
+            raise ValueError(f"{fn}: material must be a bool, not {material!r}")
+        if material and (own["probes"] > 0 or own["normalise"] is not None or own["table"]):
+            raise ValueError(f"{fn}: material=True together with probes > 0, normalise= or table= is not built yet (DESIGN.md section 11): "
+                             f"a shader reads the surface colour or probes the scene / is normalised by the frame / reads a lookup table")
     if "table" in own:
         table, taps = own["table"], own["table_taps"]
         if not isinstance(table, str):
@@ -452,6 +500,16 @@ def _register(kind: str, cls, *, params, hip: str, **own):
                              f"float* gtheta, rm::TableGrad& gt)` (found tab: {has_tab}, gt: {has_gt})")
         if not table and (has_tab or has_gt):
             raise ValueError(f"{fn}: the source of {cls.__name__} takes a rm::Table / rm::TableGrad, but no table= was given")
+    if "material" in own:
+        material = own["material"]
+        has_m, has_gm = _material_arguments(hip, name)
+        if material and not (has_m and has_gm):
+            raise ValueError(f"{fn}: material=True, but the source of {cls.__name__} does not define `template <bool Fast> RM_DEV rm::V3 "
+                             f"{name}_fwd(const rm::ShadeIn& s, const float* theta, rm::V3 m)` and `template <bool Fast> RM_DEV void "
+                             f"{name}_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 m, rm::V3 g, rm::ShadeGrad& gs, float* gtheta, "
+                             f"rm::V3& gm)` (found m: {has_m}, gm: {has_gm})")
+        if not material and has_gm:
+            raise ValueError(f"{fn}: the source of {cls.__name__} takes a surface colour (rm::V3 m / rm::V3& gm), but material=True was not given")
     if row.out_pair and has_out != callable(getattr(cls, "out", None)):
         raise TypeError(f"{fn}: {cls.__name__} " + (
             f"has no out(values, points) method, but its source defines {name}_out_fwd / {name}_out_vjp" if has_out else
@@ -474,7 +532,9 @@ def _register(kind: str, cls, *, params, hip: str, **own):
                              + (f" (normalise={old.normalise!r} before, normalise={spec.normalise!r} now)"
                                 if row.finish_pair and old.normalise != spec.normalise else "")
                              + (f" (table={old.table!r}, table_taps={old.table_taps} before, table={spec.table!r}, table_taps={spec.table_taps} now)"
-                                if "table" in own and (old.table, old.table_taps) != (spec.table, spec.table_taps) else ""))
+                                if "table" in own and (old.table, old.table_taps) != (spec.table, spec.table_taps) else "")
+                             + (f" (material={old.material} before, material={spec.material} now)"
+                                if "material" in own and old.material != spec.material else ""))
         return cls
     for other in _registry.values():
         if other.name == spec.name:          # (a scene's user types and the shader are compiled into one translation unit)
@@ -571,7 +631,7 @@ def warp_child(node, spec: UserWarp):
 
 
 def register_shader(cls, *, params=(), hip: str, probes: int = 0, chained: bool = False, normalise=None, table: str = "",
-                    table_taps: int = 0):
+                    table_taps: int = 0, material: bool = False):
     """Make instances of ``cls`` (an ``nn.Module`` subclass) usable as the ``mode`` of ``RenderLoop.forward``: a per-pixel shader
     that runs fused at the end of the frame kernels and in the fused backward.
 
@@ -593,13 +653,16 @@ def register_shader(cls, *, params=(), hip: str, probes: int = 0, chained: bool 
             gt`` at its end (module docstring: "lookup tables").  A Parameter table is NOT listed in ``params``; it receives its ``.grad``
             through a deterministic scatter.  Not together with ``probes`` or ``normalise`` (not built yet).
     table_taps: T, 1 to 4: the most table rows one pixel's VJP contributes to (1: a nearest lookup, 2: a linear interpolation).
+    material: the shader reads the surface colour of the scene's material nodes at the hit point: NAME_fwd / NAME_vjp take ``rm::V3 m``
+            behind theta and the VJP ``rm::V3& gm`` at its end, and ``forward`` takes a trailing ``material[..., 3]`` (module docstring:
+            "material nodes").  Not together with ``probes``, ``normalise`` or ``table`` (not built yet).
 
     ``cls`` has ``forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals) -> [..., 3]``,
     the first six arguments of the reference's ``Shader.forward`` (``camera_orientation`` [N,4], ``pixel_frames`` [N,3,3]); it is
     the CPU statement of the shader and is NOT replaced.  Registering a class again with the same source is a no-op; with other
     source, parameters, number of probes or value of ``chained`` / ``normalise`` / ``table`` / ``table_taps`` it is an error.  Identifiers are unique across all four kinds (leaves, combinators, warps and shaders)."""
     return _register("shader", cls, params=params, hip=hip, probes=probes, chained=chained, normalise=normalise, table=table,
-                     table_taps=table_taps)
+                     table_taps=table_taps, material=material)
 
 
 def shader_spec(node):

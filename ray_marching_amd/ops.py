@@ -157,6 +157,43 @@ class SDFEval(torch.autograd.Function):
         return gprm[: prm.numel()], gp, None
 
 
+class SurfaceAlbedo(torch.autograd.Function):
+    """contrib.surface_albedo: rm_material_forward / rm_material_backward.  The albedos are the only differentiable inputs
+    (the blend weights are constants); the kernels read every parameter in place, the albedos included."""
+
+    @staticmethod
+    def forward(ctx, points, cs: CompiledScene, *albedos):
+        _require_device(points, "points")
+        dev = points.device
+        pts = _f32c(points).reshape(-1, 3)
+        n = pts.shape[0]
+        out = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            s, keep = cs.scene_struct(None, dev)
+            _ck(cs, cs.lib().rm_material_forward(s, _abi.ptr(pts), _abi.ptr(out), n, _abi.current_stream(dev)),
+                "rm_material_forward")
+        ctx.cs = cs
+        ctx.save_for_backward(pts)
+        return out.view(*points.shape[:-1], 3)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (pts,) = ctx.saved_tensors
+        cs, dev = ctx.cs, pts.device
+        n = pts.shape[0]
+        spans = [(off, cs.leaves[i]) for i, off in cs.albedo_leaves]
+        if n == 0:
+            return (None, None, *(torch.zeros_like(p) for _, p in spans))
+        g = _f32c(grad_out).reshape(-1, 3)
+        gprm = torch.empty(max(cs.n_params, 1), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            s, keep = cs.scene_struct(None, dev)
+            part = _partials(cs, s, dev)
+            _ck(cs, cs.lib(True).rm_material_backward(s, _abi.ptr(pts), _abi.ptr(g), _abi.ptr(gprm), _abi.ptr(part), n,
+                                                      _abi.current_stream(dev)), "rm_material_backward")
+        return (None, None, *(gprm[off:off + 3].to(p.dtype) for off, p in spans))
+
+
 def scene_bound(scene, device=None):
     """Bounding sphere of a scene (an SDF module or a CompiledScene), as the kernels derive it from the live parameters
     (rm_scene_bound): ``(centre[3], R, slope, Ru, uslope)`` with  scene(p) >= slope |p - centre| - R  for every p and, where

@@ -208,6 +208,15 @@ def _shader_passes(cs: CompiledScene) -> str:
             "template <bool Fast> RM_DEV void user_shader_vjp(const ShadeIn& s, const float* theta, const Table& tab, V3 g, ShadeGrad& gs, "
             "float* gtheta, TableGrad& gt) {\n"
             f"  {name}_vjp<Fast>(s, theta, tab, g, gs, gtheta, gt);\n}}\n")
+    if cs.user_shader_material:     # (register_shader(material=True): never with probes, a table or a second pass; the pair carries m and gm)
+        return (
+            head + "#define RM_USER_SHADER_MATERIAL 1\n"
+            + f"// user shader: {name}, {floats} parameter floats, reads the surface colour, sha1 {sha}\n{cs.user_shader_source.strip()}\n"
+            "template <bool Fast> RM_DEV V3 user_shader_fwd(const ShadeIn& s, const float* theta, V3 m) {\n"
+            f"  return {name}_fwd<Fast>(s, theta, m);\n}}\n"
+            "template <bool Fast> RM_DEV void user_shader_vjp(const ShadeIn& s, const float* theta, V3 m, V3 g, ShadeGrad& gs, "
+            "float* gtheta, V3& gm) {\n"
+            f"  {name}_vjp<Fast>(s, theta, m, g, gs, gtheta, gm);\n}}\n")
     if not k:
         return (
             head
@@ -242,12 +251,20 @@ def _shader_passes(cs: CompiledScene) -> str:
         f"  {name}_vjp<Fast>(s, theta, d, g, gs, gtheta, gd);\n}}\n")
 
 
+def _material_section(cs: CompiledScene) -> str:
+    """What switches the material sweeps on (csrc/rm_device.h: RM_OP_MATERIAL in the reverse machine, Scene::material_colour /
+    material_grads; csrc/rm_kernels.h: k_material_fwd / k_material_bwd), for the same first inclusion as the user nodes'
+    sections.  Only scenes that hold a contrib.SDFMaterial get it: every other header is what it always was."""
+    return f"#define RM_MATERIALS {cs.materials}\n"
+
+
 def user_names(cs: CompiledScene):
     """(names, what) of the user types of a scene, for messages: leaf-only scenes read as they always did."""
     kinds = [("leaves", [name for name, _, _ in cs.user_leaves]),
              ("combinators", list(dict.fromkeys(name for name, _, _, _ in cs.user_combinators))),
              ("warps", [name for name, _, _, _ in cs.user_warps]),
-             ("shaders", [name for name in cs.user_shader[:1]])]
+             ("shaders", [name for name in cs.user_shader[:1]]),
+             ("material nodes", ["SDFMaterial"] if cs.materials else [])]
     kinds = [(what, names) for what, names in kinds if names]
     if len(kinds) <= 1:
         what, names = kinds[0] if kinds else ("leaves", [])
@@ -271,7 +288,7 @@ def code_header(cs: CompiledScene) -> str:
     if not cs.has_user_types:
         return head + "#ifndef RM_STATIC_CODE_LEAVES\n" + program + "#endif\n"
     user = ((_leaf_section(cs) if cs.user_leaves else "") + (_combinator_section(cs) if cs.user_combinators else "")
-            + (_warp_section(cs) if cs.user_warps else ""))
+            + (_warp_section(cs) if cs.user_warps else "") + (_material_section(cs) if cs.materials else ""))
     shader = _shader_section(cs) if cs.user_shader else ""
     return (head + "#if defined(RM_STATIC_CODE_SHADER)\n" + shader + "#elif defined(RM_STATIC_CODE_LEAVES)\n" + user
             + "#else\n" + program + "#endif\n")
@@ -465,7 +482,7 @@ def ensure(module_or_cs):
 def default_scenes():
     from .scene import scene_registry as R
     from .scene.primitives import SDFSphere
-    from .contrib import make_carved_scene, make_link_scene, make_warped_scene
+    from .contrib import make_carved_scene, make_link_scene, make_painted_scene, make_warped_scene
     return {
         "link_scene": make_link_scene(),
         "bounded_link_scene": make_link_scene(bounded=True),
@@ -477,6 +494,7 @@ def default_scenes():
         "carved_scene": make_carved_scene(),
         "warped_scene": make_warped_scene(),
         "bounded_warped_scene": make_warped_scene(bounded=True),
+        "painted_scene": make_painted_scene(),
     }
 
 
