@@ -500,6 +500,28 @@ int rm_render_backward_table(const RmScene* scene, const RmCamera* cam, const Rm
                              int32_t* tile_cost, float* hard_ws, int64_t hard_capacity, float* table_records, void* stream);
 int rm_table_scatter(const float* records, int64_t n_records, int32_t table_rows, float* grad_table, float* partials, void* stream);
 
+/* A user shader that traces a secondary ray (extensions.register_shader(trace=S), 1 <= S <= 64): the library of such a (scene,
+ * shader) pair reports S from rm_user_shader_trace() (every other library 0).  The forward needs nothing new.  The backward
+ * recomputes the secondary march and checkpoints it: one float4 {p_i, d_i} per step and LAUNCHED LANE (not per pixel), step-major,
+ * in a workspace of the caller's, private to the launch while it runs and holding nothing afterwards.
+ * rm_trace_ws_floats: an upper bound, in floats, for any rm_render_backward_trace of that frame shape by this library in this
+ * process (0 in a library without such a shader).
+ * rm_render_backward_trace: rm_render_backward_table with the workspace.  A library whose shader traces answers RM_E_BADARG (no
+ * launch) to RM_MODE_USER with trace_ws NULL, not 16-byte aligned or of fewer floats than the launch needs -- rm_render_backward
+ * and rm_render_backward_table, which pass NULL, therefore too --; every other library (and every other mode) answers
+ * RM_E_BADARG to a non-NULL trace_ws. */
+int rm_user_shader_trace(void);
+int64_t rm_trace_ws_floats(int32_t num_cameras, int32_t rows, int32_t width, int32_t flags);
+int rm_render_backward_trace(const RmScene* scene, const RmCamera* cam, const RmTetra* tetra,
+                             const float* orientation, const float* translation,
+                             const float* traj, const int32_t* nexec, const float* p_final, const float* normal_u,
+                             const float* grad_image, float* grad_params, float* partials, uint32_t* work,
+                             float* grad_pos, float* grad_dirs, float* grad_qdir,
+                             const void* cmap, int32_t cmap_size, int32_t cmap_dtype,
+                             int32_t mode, int32_t degree, int32_t steps, int32_t row_begin, int32_t row_end, int32_t flags,
+                             int32_t* tile_cost, float* hard_ws, int64_t hard_capacity, float* table_records,
+                             float* trace_ws, int64_t trace_ws_floats, void* stream);
+
 /* out[width] = sum over n_rows rows of rows[n_rows][width], fixed summation tree (deterministic). */
 int rm_sum_rows(const float* rows, int64_t n_rows, int32_t width, float* out, void* stream);
 

@@ -117,6 +117,13 @@ _SIGNATURES = {
                                            _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                            _P, _P, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P]),
+    "rm_user_shader_trace": (C.c_int, []),
+    "rm_trace_ws_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "rm_render_backward_trace": (C.c_int, [C.POINTER(RmScene), C.POINTER(RmCamera), C.POINTER(RmTetra), _P, _P,
+                                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P,
+                                           _P, C.c_int64, _P]),
     "rm_table_scatter": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P]),
     "rm_sum_rows": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P]),
     "rm_shade_norm_backward": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int64, _P]),

@@ -135,6 +135,7 @@ class CompiledScene:
     user_shader_table: str = ""         # the attribute that holds its lookup table (register_shader(table=...)); "": none
     user_shader_table_taps: int = 0     # T: the most table rows one pixel's VJP contributes to; 0: no table
     user_shader_material: bool = False  # its pair takes the surface colour of the material nodes (register_shader(material=True))
+    user_shader_trace: int = 0          # S: the steps of the secondary ray the frame kernels march for it (register_shader(trace=S)); 0: none
     materials: int = 0                  # RM_OP_MATERIAL instructions, the implicit ones included (contrib.SDFMaterial); 0: none, the scene
                                         # is what it always was.  > 0: the scene runs only through its specialised library (RM_MATERIALS)
     shader_offset: int = 0              # where its theta starts in the block (= the scene's own n_params)
@@ -535,7 +536,7 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
         table[id(p)] = cursor
         cursor += p.numel()
     shader_offset, user_shader, shader_source, shader_probes, shader_chained, shader_normalise = cursor, (), "", 0, False, None
-    shader_table, shader_table_taps, shader_material = "", 0, False
+    shader_table, shader_table_taps, shader_material, shader_trace = "", 0, False, 0
     if shader is not None:
         spec = shader_spec(shader)
         if spec is None:
@@ -549,7 +550,7 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
             cursor += p.numel()
         user_shader, shader_source, shader_probes = (spec.name, cursor - shader_offset, spec.sha1), spec.hip, spec.probes
         shader_chained, shader_normalise = spec.chained, spec.normalise
-        shader_table, shader_table_taps, shader_material = spec.table, spec.table_taps, spec.material
+        shader_table, shader_table_taps, shader_material, shader_trace = spec.table, spec.table_taps, spec.material, spec.trace
     n_params = cursor                 # (derived constants start behind the shader's floats)
     em = _Emitter(table)
     # derived block = [capsule constants of every SDFLine (gradients flow through them) | cull bounds, bound tables]
@@ -581,6 +582,8 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
         slots.append(("table", shader_table, shader_table_taps))
     if shader_material:               # (... and one that reads the surface colour: its pair takes m / gm)
         slots.append(("material",))
+    if shader_trace:                  # (... and one that traces a secondary ray: S is a constant of its header, like the probes' K)
+        slots.append(("trace", shader_trace))
     signature = (tuple(map(tuple, program.tolist())), n_params, em.n_derived, em.max_depth, em.n_slots, em.n_grad_derived, *slots)
     return CompiledScene(program=program, leaves=leaves, leaf_names=names, leaf_offsets=offsets,
                          n_params=n_params, n_derived=em.n_derived, n_grad_derived=em.n_grad_derived, stack_floats=em.max_depth,
@@ -594,7 +597,7 @@ def compile_scene(module: nn.Module, shader: nn.Module = None) -> CompiledScene:
                          user_shader_probes=shader_probes, user_shader_chained=shader_chained,
                          user_shader_normalise=shader_normalise, user_shader_table=shader_table,
                          user_shader_table_taps=shader_table_taps, materials=em.materials,
-                         user_shader_material=shader_material)
+                         user_shader_material=shader_material, user_shader_trace=shader_trace)
 
 
 def structure_key(module: nn.Module):

@@ -1255,3 +1255,121 @@ template <bool Fast> RM_DEV void material_lambert_vjp(const rm::ShadeIn& s, cons
 """
 
 register_shader(MaterialLambertShader, params=("ambient",), hip=_MATERIAL_LAMBERT_HIP, material=True)
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# Shaders that trace a secondary ray (register_shader(trace=S)): the frame kernels sphere-trace it and hand back the hit
+# --------------------------------------------------------------------------------------------------------------------
+class MirrorShader(nn.Module):
+    """A distant light on a partly mirroring surface: the primary ray is reflected at the hit point, ``v2 = v - 2 (v . n) n`` from
+    ``o2 = p + bias n``, and sphere-traced 24 steps through the scene.  With ``c(n) = ambient + (1 - ambient) clamp(-(l . n), 0, 1)``,
+    the directional-light term for the normalised ``light_direction`` ``l``, and the hit weight ``w = clamp(1 - h.d / hit_eps, 0, 1)`` of
+    the secondary ray's end point (1 on a surface, 0 where the scene is further than ``hit_eps`` away), the pixel is
+
+        rgb = (1 - reflectivity) c(n) + reflectivity (w c(h.n) + (1 - w) sky).
+
+    Eight trainable floats (``reflectivity``, ``light_direction`` [3], ``ambient``, ``sky`` [3]); ``bias`` and ``hit_eps`` are constructor
+    constants kept as frozen ``nn.Parameter``s (``requires_grad = False``) so that their values travel in ``theta``.  Both clamps pass
+    their gradient on the closed interval.  No transcendental function.
+
+    ``trace``: a callable ``(origins[..., 3], directions[..., 3]) -> (points, normals, values[..., 1])`` (extensions.reference_trace)."""
+
+    def __init__(self, reflectivity: float = 0.5, light_direction=(0.0, 0.0, 1.0), ambient: float = 0.15, sky=(0.5, 0.6, 0.8),
+                 bias: float = 0.05, hit_eps: float = 0.25) -> None:
+        super().__init__()
+        self.reflectivity = nn.Parameter(torch.tensor(reflectivity, dtype=torch.float32))
+        self.light_direction = nn.Parameter(torch.tensor(light_direction, dtype=torch.float32))
+        self.ambient = nn.Parameter(torch.tensor(ambient, dtype=torch.float32))
+        self.sky = nn.Parameter(torch.tensor(sky, dtype=torch.float32))
+        self.bias = nn.Parameter(torch.tensor(bias, dtype=torch.float32), requires_grad=False)
+        self.hit_eps = nn.Parameter(torch.tensor(hit_eps, dtype=torch.float32), requires_grad=False)
+
+    def forward(self, px_coords: Tensor, camera_orientation: Tensor, pixel_frames: Tensor, ray_directions: Tensor,
+                surface_coords: Tensor, surface_normals: Tensor, trace) -> Tensor:
+        light = self.light_direction / torch.linalg.vector_norm(self.light_direction)
+
+        def lit(normals):
+            return self.ambient + (1 - self.ambient) * (normals * light).sum(dim=-1, keepdim=True).neg().clamp(0, 1)
+
+        vn = (ray_directions * surface_normals).sum(dim=-1, keepdim=True)
+        _, hit_normals, hit_values = trace(surface_coords + self.bias * surface_normals, ray_directions - (2 * vn) * surface_normals)
+        w = (1 - hit_values / self.hit_eps).clamp(0, 1)
+        reflected = w * lit(hit_normals) + (1 - w) * self.sky
+        return (1 - self.reflectivity) * lit(surface_normals) + self.reflectivity * reflected
+
+
+# theta = {reflectivity, light_direction[3], ambient, sky[3], bias, hit_eps}; the forward restates the ATen op stream above, the two
+# VJPs are autograd's, written out (NAME_vjp writes gtheta, NAME_ray_vjp adds to it: bias and hit_eps are frozen and get nothing)
+_MIRROR_SHADER_HIP = r"""
+template <bool Fast> RM_DEV void mirror_ray(const rm::ShadeIn& s, const float* theta, rm::TraceRay& r) {
+  const float k = 2.0f * dot_seq(s.v, s.n);
+  r.o = mk3(s.p.x + theta[8] * s.n.x, s.p.y + theta[8] * s.n.y, s.p.z + theta[8] * s.n.z);
+  r.v = mk3(s.v.x - k * s.n.x, s.v.y - k * s.n.y, s.v.z - k * s.n.z);
+}
+template <bool Fast> RM_DEV void mirror_ray_vjp(const rm::ShadeIn& s, const float* theta, const rm::TraceRay& gr, rm::ShadeGrad& gs,
+                                                float* gtheta) {
+  // o2 = p + bias n
+  gs.p = gs.p + gr.o;
+  gs.n = gs.n + theta[8] * gr.o;
+  // v2 = v - k n, k = 2 (v . n)
+  const float k = 2.0f * dot_seq(s.v, s.n);
+  const float gk = -dot_seq(gr.v, s.n);
+  const float gvn = 2.0f * gk;
+  gs.v = (gs.v + gr.v) + gvn * s.n;
+  gs.n = (gs.n - k * gr.v) + gvn * s.v;
+}
+template <bool Fast> RM_DEV rm::V3 mirror_fwd(const rm::ShadeIn& s, const float* theta, const rm::TraceHit& h) {
+  const rm::V3 L = mk3(theta[1], theta[2], theta[3]);
+  const float ln = norm3(L);
+  const rm::V3 l = mk3(L.x / ln, L.y / ln, L.z / ln);
+  const float a = theta[4];
+  const float cs = a + (1.0f - a) * t_clamp(-dot_seq(s.n, l), 0.0f, 1.0f);
+  const float ch = a + (1.0f - a) * t_clamp(-dot_seq(h.n, l), 0.0f, 1.0f);
+  const float w = t_clamp(1.0f - h.d / theta[9], 0.0f, 1.0f);
+  const float wc = w * ch, u = 1.0f - w;
+  const float local = (1.0f - theta[0]) * cs;
+  return mk3(local + theta[0] * (wc + u * theta[5]), local + theta[0] * (wc + u * theta[6]), local + theta[0] * (wc + u * theta[7]));
+}
+template <bool Fast> RM_DEV void mirror_vjp(const rm::ShadeIn& s, const float* theta, const rm::TraceHit& h, rm::V3 g, rm::ShadeGrad& gs,
+                                            float* gtheta, rm::TraceGrad& gh) {
+  const rm::V3 L = mk3(theta[1], theta[2], theta[3]);
+  const float ln = norm3_t<Fast>(L);
+  const rm::V3 l = mk3(div_t<Fast>(L.x, ln), div_t<Fast>(L.y, ln), div_t<Fast>(L.z, ln));
+  const float a = theta[4], rho = theta[0];
+  const float es = -dot_seq(s.n, l), eh = -dot_seq(h.n, l);
+  const float ms = t_clamp(es, 0.0f, 1.0f), mh = t_clamp(eh, 0.0f, 1.0f);
+  const float cs = a + (1.0f - a) * ms, ch = a + (1.0f - a) * mh;
+  const float x = 1.0f - div_t<Fast>(h.d, theta[9]);
+  const float w = t_clamp(x, 0.0f, 1.0f), u = 1.0f - w;
+  const float wc = w * ch;
+  const float gsum = (g.x + g.y) + g.z;
+  // rgb = (1 - rho) cs + rho refl, refl = w ch + (1 - w) sky
+  gtheta[0] = ((g.x * (wc + u * theta[5]) + g.y * (wc + u * theta[6])) + g.z * (wc + u * theta[7])) - gsum * cs;
+  const float gcs = gsum * (1.0f - rho);
+  const rm::V3 gr = rho * g;
+  gtheta[5] = gr.x * u; gtheta[6] = gr.y * u; gtheta[7] = gr.z * u;
+  const float grs = (gr.x + gr.y) + gr.z;
+  const float gch = grs * w;
+  const float gw = grs * ch - ((gr.x * theta[5] + gr.y * theta[6]) + gr.z * theta[7]);
+  // w = clamp(1 - d / hit_eps, 0, 1): the clamp passes the gradient on the closed interval
+  const float gx = (x >= 0.0f && x <= 1.0f) ? gw : 0.0f;
+  gh.d = -div_t<Fast>(gx, theta[9]);
+  // c = a + (1 - a) m, m = clamp(e, 0, 1), e = -(n . l), for the surface normal and for the hit's
+  gtheta[4] = (gcs - gcs * ms) + (gch - gch * mh);
+  const float gms = gcs * (1.0f - a), gmh = gch * (1.0f - a);
+  const float ges = (es >= 0.0f && es <= 1.0f) ? gms : 0.0f;
+  const float geh = (eh >= 0.0f && eh <= 1.0f) ? gmh : 0.0f;
+  gs.n = gs.n - ges * l;
+  gh.n = gh.n - geh * l;
+  // l = L / |L|: dL = (gl - l (gl . l)) / |L|
+  const rm::V3 gl = neg(ges * s.n + geh * h.n);
+  const float gll = dot_seq(gl, l);
+  gtheta[1] = div_t<Fast>(gl.x - l.x * gll, ln);
+  gtheta[2] = div_t<Fast>(gl.y - l.y * gll, ln);
+  gtheta[3] = div_t<Fast>(gl.z - l.z * gll, ln);
+  gtheta[8] = 0.0f; gtheta[9] = 0.0f;                            // bias, hit_eps: constants (frozen), no gradient
+}
+"""
+
+register_shader(MirrorShader, params=("reflectivity", "light_direction", "ambient", "sky", "bias", "hit_eps"), hip=_MIRROR_SHADER_HIP,
+                trace=24)

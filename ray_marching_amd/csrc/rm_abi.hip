@@ -215,6 +215,14 @@ int rm_user_shader_table(void) {
 #endif
 }
 
+int rm_user_shader_trace(void) {
+#ifdef RM_USER_SHADER_TRACE
+  return RM_USER_SHADER_TRACE;
+#else
+  return 0;
+#endif
+}
+
 // RM_MODE_USER of a library whose shader reads a lookup table: the table in the colormap slot (float32 [2..RM_TABLE_MAX_ROWS, 3])
 static bool user_table_ok([[maybe_unused]] int mode, [[maybe_unused]] const void* cmap, [[maybe_unused]] int cmap_size,
                           [[maybe_unused]] int cmap_dtype) {
@@ -230,6 +238,24 @@ int64_t rm_grad_partials_floats(const RmScene* scene, int64_t n) {
   if (!scene) return 0;
   (void)n;
   return (int64_t)(kPartialRows + 1) * (scene->n_params + scene->n_grad_derived);
+}
+
+// wave tiles of a frame: 8x8 pixel tiles (RM_FLAG_TILE8X8) or runs of 64 rays
+static int64_t wave_tile_count(int32_t num_cameras, int32_t rows, int32_t width, int32_t flags) {
+  return (flags & RM_FLAG_TILE8X8) ? (int64_t)num_cameras * ((width + 7) >> 3) * ((rows + 7) >> 3)
+                                   : ((int64_t)num_cameras * rows * width + 63) / 64;
+}
+
+// lanes a backward launch of this frame shape starts at most: blocks of at most 128 threads, one wave tile per wave, the grid
+// capped at tune_bwd_blocks()
+static int64_t bwd_lanes_bound(int64_t wave_tiles) {
+  const int64_t by_tiles = (wave_tiles + 1) * 64, by_grid = (int64_t)tune_bwd_blocks() * 128;
+  return by_tiles < by_grid ? by_tiles : by_grid;
+}
+
+int64_t rm_trace_ws_floats(int32_t num_cameras, int32_t rows, int32_t width, int32_t flags) {
+  if (rm_user_shader_trace() == 0 || num_cameras <= 0 || rows <= 0 || width <= 0) return 0;
+  return 4 * (int64_t)rm_user_shader_trace() * bwd_lanes_bound(wave_tile_count(num_cameras, rows, width, flags));
 }
 
 int64_t rm_bwd_hard_floats(int64_t capacity, int32_t steps) {
@@ -399,11 +425,6 @@ static int check_render(const RmScene* scene, const RmCamera* cam, const RmTetra
   if (steps < 0 || row_begin < 0 || row_end > cam->height || row_begin >= row_end)
     return fail(RM_E_BADARG, "render: bad steps/rows (%d, [%d,%d) of %d)", steps, row_begin, row_end, cam->height);
   return RM_OK;
-}
-
-static int64_t wave_tile_count(int32_t num_cameras, int32_t rows, int32_t width, int32_t flags) {
-  return (flags & RM_FLAG_TILE8X8) ? (int64_t)num_cameras * ((width + 7) >> 3) * ((rows + 7) >> 3)
-                                   : ((int64_t)num_cameras * rows * width + 63) / 64;
 }
 
 int64_t rm_wave_tiles(int32_t num_cameras, int32_t rows, int32_t width, int32_t flags) {
@@ -718,9 +739,30 @@ int rm_render_backward_table(const RmScene* scene, const RmCamera* cam, const Rm
                              int32_t cmap_dtype, int32_t mode, int32_t degree,
                              int32_t steps, int32_t row_begin, int32_t row_end, int32_t flags, int32_t* tile_cost,
                              float* hard_ws, int64_t hard_capacity, float* table_records, void* stream) {
+  return rm_render_backward_trace(scene, cam, tetra, orientation, translation, traj, nexec, p_final, normal_u, grad_image, grad_params,
+                                  partials, work, grad_pos, grad_dirs, grad_qdir, cmap, cmap_size, cmap_dtype, mode, degree, steps,
+                                  row_begin, row_end, flags, tile_cost, hard_ws, hard_capacity, table_records, nullptr, 0, stream);
+}
+
+int rm_render_backward_trace(const RmScene* scene, const RmCamera* cam, const RmTetra* tetra, const float* orientation,
+                             const float* translation, const float* traj, const int32_t* nexec, const float* p_final,
+                             const float* normal_u, const float* grad_image, float* grad_params, float* partials, uint32_t* work,
+                             float* grad_pos, float* grad_dirs, float* grad_qdir, const void* cmap, int32_t cmap_size,
+                             int32_t cmap_dtype, int32_t mode, int32_t degree,
+                             int32_t steps, int32_t row_begin, int32_t row_end, int32_t flags, int32_t* tile_cost,
+                             float* hard_ws, int64_t hard_capacity, float* table_records, float* trace_ws, int64_t trace_ws_floats,
+                             void* stream) {
 #ifdef RM_NO_BACKWARD
   return fail(RM_E_BADARG, "rm_render_backward: this specialised library was built forward-only");
 #else
+  // (the workspace first: what a library has no use for, or cannot do without, is refused whatever else the call holds)
+  const bool tracing = rm_user_shader_trace() > 0 && mode == RM_MODE_USER;
+  if (trace_ws && !tracing)
+    return fail(RM_E_BADARG, "rm_render_backward_trace: trace_ws is written by RM_MODE_USER of a library whose user shader traces a "
+                             "secondary ray (rm_user_shader_trace() > 0), not by this one");
+  if (tracing && (!trace_ws || (reinterpret_cast<uintptr_t>(trace_ws) & 15)))
+    return fail(RM_E_BADARG, "rm_render_backward_trace: this library's user shader traces a secondary ray of %d steps: its backward needs "
+                             "trace_ws (16-byte aligned, rm_trace_ws_floats floats)", rm_user_shader_trace());
   if (int e = check_render(scene, cam, tetra, orientation, translation, steps, row_begin, row_end)) return e;
   if (cam->dtype != RM_DTYPE_F32) return fail(RM_E_BADARG, "rm_render_backward: fp32 camera buffers only");
   const bool mapped = (mode == RM_MODE_TANGENT || mode == RM_MODE_SPIN);
@@ -754,6 +796,13 @@ int rm_render_backward_table(const RmScene* scene, const RmCamera* cam, const Rm
   // every wave would end on a look at all of them -- static stride instead (same-box: 0.340 -> 0.329 ms per step at 512^2;
   // at 1024^2, 8 tiles per wave, the queues win by 2 %: profiles/r03_train_ab.txt)
   if (wave_tiles <= 2 * (int64_t)grid * (L.block >> 6) && !env_set("RM_BWD_DYNAMIC_TILES")) a.flags &= ~RM_FLAG_DYNAMIC_TILES;
+  if (tracing) {      // one float4 per step and launched lane
+    const int64_t need = 4 * (int64_t)rm_user_shader_trace() * grid * L.block;
+    if (trace_ws_floats < need)
+      return fail(RM_E_BADARG, "rm_render_backward_trace: trace_ws holds %lld floats, this launch (%d blocks of %d lanes, %d steps) needs "
+                               "%lld (rm_trace_ws_floats)", (long long)trace_ws_floats, grid, L.block, rm_user_shader_trace(), (long long)need);
+    a.trace_ws = trace_ws;
+  }
   // deferred rays: only with the reverse early exit, a workspace for the list and its counter
   const bool defer = hard_ws && hard_capacity > 0 && work && (flags & RM_FLAG_EARLY_OUT) && steps > 0;
   if (defer) {

@@ -854,6 +854,9 @@ struct RenderArgs {
   int32_t hard_cap;
   // backward of a user shader with a lookup table (RM_USER_SHADER_TABLE), nullable: [R][T][4] records (row, dL/d(row)) for k_table_scatter
   float* table_records;
+  // backward of a user shader that traces a secondary ray (RM_USER_SHADER_TRACE): the checkpoints of the secondary march,
+  // [S][launched lanes] float4 {p_i, d_i}, step-major (a wave's access at one step is one contiguous 1 KiB run); null elsewhere
+  float* trace_ws;
 };
 
 #define RM_WORK_HARD_COUNT 32      // workspace word (own 128-B line): rays deferred by k_render_bwd
@@ -1068,6 +1071,14 @@ struct TableGrad {
   V3 g[RM_USER_SHADER_MAX_TABLE_TAPS] = {};
 };
 
+// The secondary ray of a user shader that traces one (register_shader(trace=S)): origin and direction as NAME_ray writes them
+// (the direction is used as given, unit or not), and what the frame kernels hand back after S sphere-tracing steps along it:
+// the end point p = p_S, the tetrahedral normal n there and the scene's value d = scene(p_S).  TraceGrad: dL/d(TraceHit).
+#define RM_USER_SHADER_MAX_TRACE_STEPS 64
+struct TraceRay { V3 o, v; };
+struct TraceHit { V3 p, n; float d; };
+struct TraceGrad { V3 p, n; float d; };
+
 // User-defined per-pixel shader (RM_MODE_USER; extensions.register_shader).  The code header of a specialised library is
 // included a third time here, behind ShadeIn / ShadeGrad and still inside namespace rm, for its shader section alone
 // (RM_STATIC_CODE_LEAVES keeps the program section of a header without one out):
@@ -1160,6 +1171,36 @@ RM_DEV void user_probe_values(const SceneT& scene, const ShadeIn& si, const floa
 #endif
 #endif
 
+// A shader that traces a secondary ray (register_shader(trace=S), 1 <= S <= RM_USER_SHADER_MAX_TRACE_STEPS) adds
+//     #define RM_USER_SHADER_TRACE S,
+//     template <bool Fast> RM_DEV void NAME_ray    (const rm::ShadeIn& s, const float* theta, rm::TraceRay& r);
+//     template <bool Fast> RM_DEV void NAME_ray_vjp(const rm::ShadeIn& s, const float* theta, const rm::TraceRay& gr, rm::ShadeGrad& gs, float* gtheta);
+// (user_shader_ray / user_shader_ray_vjp forward to them), and its NAME_fwd / NAME_vjp take `const rm::TraceHit& h` behind theta (the
+// VJP also `rm::TraceGrad& gh` at its end).  The march is SDFMarcher's recurrence with the full evaluator, p_0 = r.o, p_{i+1} =
+// scene(p_i) * r.v + p_i, S steps and no early exit: one rolled loop of S + 1 evaluations (one inlined copy of the scene), then
+// the loop's own tetrahedron at p_S.  kStore (the backward): step i leaves float4{p_i, d_i} at ws[i * stride], a checkpoint
+// buffer in global memory that is private to the lane -- the same lane reads it back in the reverse sweep, so nothing is fenced.
+#ifdef RM_USER_SHADER_TRACE
+static_assert(RM_USER_SHADER_TRACE >= 1 && RM_USER_SHADER_TRACE <= RM_USER_SHADER_MAX_TRACE_STEPS, "trace: 1 <= S <= 64");
+template <bool kStore, class SceneT>
+RM_DEV void user_trace_hit(const SceneT& scene, const Tetra& T, const TraceRay& r, TraceHit& h, V3* u_out = nullptr,
+                           [[maybe_unused]] float4* ws = nullptr, [[maybe_unused]] int64_t stride = 0) {
+  V3 p = r.o;
+  float d = 0.0f;
+#pragma unroll 1
+  for (int i = 0; i <= RM_USER_SHADER_TRACE; ++i) {
+    d = scene.eval(p);
+    if (i < RM_USER_SHADER_TRACE) {
+      if constexpr (kStore) ws[(int64_t)i * stride] = make_float4(p.x, p.y, p.z, d);
+      p = step_point(p, r.v, d);
+    }
+  }
+  h.p = p; h.d = d;
+  float lap;
+  normals_forward(scene, T, p, d, h.n, lap, u_out);
+}
+#endif
+
 // The user shader as the forward of the frame kernels calls it: theta out of the staged block and, for a shader with probes, the
 // scene at its probe points (the one place of the forward that knows about probes); empty in a library without a user shader.
 struct UserShader {
@@ -1186,6 +1227,17 @@ struct UserShader {
 #endif
   }
   RM_DEV V3 fwd(const ShadeIn& si) const { return user_shader_fwd<false>(si, theta.v, m); }
+#elif defined(RM_USER_SHADER_TRACE)
+  // a shader that traces a secondary ray (register_shader(trace=S)): ray -> march -> value -> normal in the place of the probes,
+  // with the frame's tetrahedron, set by RM_USER_TRACE_SET in front of probe
+  const Tetra* tetra = nullptr;
+  TraceHit hit{};
+  template <class SceneT> RM_DEV void probe(const SceneT& scene, const ShadeIn& si) {
+    TraceRay r;
+    user_shader_ray<false>(si, theta.v, r);
+    user_trace_hit<false>(scene, *tetra, r, hit);
+  }
+  RM_DEV V3 fwd(const ShadeIn& si) const { return user_shader_fwd<false>(si, theta.v, hit); }
 #else
   template <class SceneT> RM_DEV void probe(const SceneT&, const ShadeIn&) {}
 #ifdef RM_USER_SHADER_TABLE
@@ -1217,6 +1269,12 @@ struct UserShader {
 #define RM_USER_TABLE_SET(us, a) (us).tab = Table{static_cast<const float*>((a).cmap), (a).cmap_size};
 #else
 #define RM_USER_TABLE_SET(us, a)
+#endif
+// ... and so is the tetrahedron of a shader that traces a secondary ray
+#ifdef RM_USER_SHADER_TRACE
+#define RM_USER_TRACE_SET(us, T) (us).tetra = &(T);
+#else
+#define RM_USER_TRACE_SET(us, T)
 #endif
 
 // third column of the camera rotation (QuaternionToSO3, quaternion.py:114-124): pixel_frames[..., 2]
@@ -1529,6 +1587,7 @@ RM_DEV void finish_tile(const RenderArgs& a, const SceneT& scene, const Tetra& T
   if (UserShader::kEnabled && mode == RM_MODE_USER) si.lap = 0.0f;       // (the taps' sum without the centre value is no Laplacian: a user shader reads 0)
   UserShader us(scene.P);
   RM_USER_TABLE_SET(us, a)
+  RM_USER_TRACE_SET(us, T)
   if (UserShader::kEnabled && mode == RM_MODE_USER) us.probe(scene, si);   // (mode is uniform: every lane of the wave evaluates)
   const Shaded sh = shade_pixel(mode, si, a.cmap_size, a.degree, &us);
   const V3 out = sh.rgb;
@@ -2520,6 +2579,36 @@ __global__ void __launch_bounds__(256) RM_BWD_OCC k_render_bwd(RenderArgs a) {
       const float minv = 1.0f / msum;
       scene.material_grads(p, (live && msum != 0.0f) ? mk3(gm.x * minv, gm.y * minv, gm.z * minv) : z3);
 #endif
+#elif defined(RM_USER_SHADER_TRACE)
+      // a shader that traces a secondary ray: the march again (the recording forward writes no buffer for it), now leaving one
+      // float4 {p_i, d_i} per step in the lane's own column of the checkpoint workspace; the shader's VJP, which also hands back
+      // dL/d(hit); the tetrahedron's and the value's VJP at p_S; then the steps last to first, g_i = lambda_{i+1} . v, lambda_i =
+      // lambda_{i+1} + scene.vjp(p_i, g_i), dL/dv += d_i lambda_{i+1}; and the ray's own VJP, which adds to gs and gtheta.  Every lane
+      // reaches every scene.vjp (S is a constant of the library); a lane without a pixel passes a zero upstream.
+      {
+        const int64_t ws_stride = (int64_t)gridDim.x * blockDim.x;
+        float4* ws = reinterpret_cast<float4*>(a.trace_ws) + ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+        TraceRay ray;
+        user_shader_ray<false>(si, theta, ray);
+        TraceHit hit;
+        V3 hu;
+        user_trace_hit<true>(scene, T, ray, hit, &hu, ws, ws_stride);
+        TraceGrad gh{z3, z3, 0.0f};
+        user_shader_vjp<(RM_FAST_VJP != 0)>(si, theta, hit, gi3, gs, gtheta, gh);
+        V3 tl = normals_backward(scene, T, hit.p, hu, live ? gh.n : z3, 0.0f, false);
+        tl = tl + scene.vjp(hit.p, live ? gh.d : 0.0f);
+        tl = live ? tl + gh.p : z3;
+        V3 tgv = z3;
+#pragma unroll 1
+        for (int i = RM_USER_SHADER_TRACE - 1; i >= 0; --i) {
+          const float4 c = ws[(int64_t)i * ws_stride];
+          const float g = (tl.x * ray.v.x + tl.y * ray.v.y) + tl.z * ray.v.z;
+          tgv = tgv + c.w * tl;
+          tl = tl + scene.vjp(mk3(c.x, c.y, c.z), g);
+          if (!live) { tl = z3; tgv = z3; }     // (a lane without a pixel keeps a zero upstream whatever ray 0's path returns, as in the primary march)
+        }
+        user_shader_ray_vjp<(RM_FAST_VJP != 0)>(si, theta, TraceRay{tl, tgv}, gs, gtheta);
+      }
 #elif defined(RM_USER_SHADER_TABLE)
       // a shader with a lookup table: its VJP also hands back up to T (row, dL/d(row)) pairs.  Where the table wants a gradient
       // (a.table_records: a run-time choice, the library is the same) the pixel's T records go out as one float4 each, at the

@@ -187,6 +187,33 @@ built-in mode, or with a shader registered without ``material=True``, renders bi
 stripped, and its albedos get zero gradients.  ``material=True`` together with ``probes``, ``normalise=`` or ``table=`` is refused at
 registration (not built yet).  Scenes with material nodes run only through their specialised library, like user nodes.
 
+*Traced rays* let a shader follow a secondary ray through the scene (a mirror reflection; a chain of probes ends at 8 because the
+whole chain lives in registers): ``register_shader(..., trace=S)`` with ``1 <= S <= RM_USER_SHADER_MAX_TRACE_STEPS`` (64).  The source
+brings two more functions and its own pair takes the hit,
+
+    template <bool Fast> RM_DEV void   NAME_ray    (const rm::ShadeIn& s, const float* theta, rm::TraceRay& r);
+    template <bool Fast> RM_DEV void   NAME_ray_vjp(const rm::ShadeIn& s, const float* theta, const rm::TraceRay& gr,
+                                                    rm::ShadeGrad& gs, float* gtheta);
+    template <bool Fast> RM_DEV rm::V3 NAME_fwd(const rm::ShadeIn& s, const float* theta, const rm::TraceHit& h);
+    template <bool Fast> RM_DEV void   NAME_vjp(const rm::ShadeIn& s, const float* theta, const rm::TraceHit& h, rm::V3 g,
+                                                rm::ShadeGrad& gs, float* gtheta, rm::TraceGrad& gh);
+
+``NAME_ray`` writes the one secondary ray of the pixel, ``rm::TraceRay {V3 o, v}``: origin and direction, the direction used as given
+(it need not be a unit vector).  The kernels march it with SDFMarcher's recurrence in its operation order and the full evaluator,
+``p_0 = r.o``, ``p_{i+1} = scene(p_i) * r.v + p_i`` for ``i < S`` -- exactly ``S`` steps, no early exit, ``S`` a constant of the (scene, shader)
+library like ``probes=K`` -- and hand ``NAME_fwd`` the hit ``rm::TraceHit {V3 p, n; float d}``: ``h.p = p_S``, ``h.d = scene(p_S)`` and ``h.n`` the
+4-tap tetrahedral normal at ``p_S`` with the loop's own tetrahedron (what SDFNormals computes).  ``NAME_vjp`` writes ``gtheta[i]`` and
+dL/d(hit) into ``gh`` (``rm::TraceGrad``, the fields of ``TraceHit``; it arrives zeroed); the kernels carry it through the normal, the
+value and every step of the secondary march -- into the scene parameters at each of them, and into the ray's origin and direction
+-- and ``NAME_ray_vjp`` ADDS ``J^T gr`` into ``gs`` and ``gtheta``, from where the primary hit and the pose get their share as for every shader.
+The backward recomputes the secondary march (the forward stores nothing for it) into a checkpoint workspace in global memory,
+one float4 per step and launched lane, which ``ops`` provides (rm_trace_ws_floats / rm_render_backward_trace).  The reverse secondary
+march sums in program order: where every ray is walked in place two backwards give the same bits (the deferred-ray list of the
+primary march, on by default, sums in the order the rays reached it, for every shader).  The class's PyTorch ``forward`` takes one more trailing argument, ``trace``, a callable ``(origins[..., 3], directions[..., 3])
+-> (points, normals, values[..., 1])`` built from plain torch ops; ``reference_trace(scene_fn, steps, normals_eps)`` builds it from any
+``points -> [..., 1]`` scene function.  ``trace=`` together with ``probes``, ``chained``, ``normalise=``, ``table=`` or ``material=`` is refused at
+registration (not built yet).
+
 Scenes that contain such a leaf, combinator or warp, and frames shaded by such a shader, run only through their per-scene specialised library (specialize.py), into which
 the source is compiled; the LDS interpreter has no handler for them and ``CompiledScene.lib()`` says so instead of
 rendering a wrong picture.
@@ -201,7 +228,7 @@ import torch
 import torch.nn as nn
 
 __all__ = ["register_leaf", "leaf_spec", "check_bound", "UserLeaf", "register_combinator", "combinator_spec", "UserCombinator",
-           "register_warp", "warp_spec", "UserWarp", "register_shader", "shader_spec", "UserShader"]
+           "register_warp", "warp_spec", "UserWarp", "register_shader", "shader_spec", "UserShader", "reference_trace"]
 
 
 @dataclass(frozen=True)
@@ -250,6 +277,7 @@ class UserShader(_UserSpec):
     table: str = ""     # attribute that holds the lookup table ([L, 3] float32 buffer or nn.Parameter; the pair takes tab / gt); "": none
     table_taps: int = 0     # T: the most table rows one pixel's VJP contributes to (1..RM_USER_SHADER_MAX_TABLE_TAPS); 0: no table
     material: bool = False  # the pair takes the surface colour of the scene's material nodes, `rm::V3 m` (and the VJP `rm::V3& gm`)
+    trace: int = 0      # S: the steps of the secondary ray the frame kernels march for it (NAME_ray / NAME_ray_vjp; the pair takes the hit); 0: none
 
 
 @dataclass(frozen=True)
@@ -268,6 +296,7 @@ class _Kind:
     bound: str = ""                 # the noun under which NAME_bound is looked for ("": the kind signs no bound)
     probe_pair: bool = False        # the source may bring NAME_probe / NAME_probe_vjp (a shader's scene probes)
     finish_pair: bool = False       # the source may bring NAME_finish / NAME_finish_vjp (a shader normalised by the frame's min / max)
+    ray_pair: bool = False          # the source may bring NAME_ray / NAME_ray_vjp (a shader that traces a secondary ray)
 
 
 _KINDS = {
@@ -296,12 +325,14 @@ _KINDS = {
         "`template <bool Fast> RM_DEV void NAME_vjp(const rm::ShadeIn& s, const float* theta, rm::V3 g, rm::ShadeGrad& gs, float* "
         "gtheta)`",
         methods=(("forward", "forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals)"),),
-        same=("sha1", "params", "probes", "chained", "normalise", "table", "table_taps", "material"), device_forward=False, probe_pair=True, finish_pair=True),
+        same=("sha1", "params", "probes", "chained", "normalise", "table", "table_taps", "material", "trace"), device_forward=False, probe_pair=True, finish_pair=True,
+        ray_pair=True),
 }
 
 NORMALISATIONS = (None, "minmax")    # register_shader(normalise=...): the frame statistics a shader may be normalised by
 RM_USER_SHADER_MAX_TABLE_TAPS = 4   # the most table rows one pixel's VJP may contribute to (gt.row[] / gt.g[] live in registers)
 RM_USER_SHADER_MAX_TABLE_ROWS = 4096    # the longest lookup table (the size of the reference's own colormap: 48 KB of float32)
+RM_USER_SHADER_MAX_TRACE_STEPS = 64  # the most steps of a shader's secondary ray (one float4 of the backward's checkpoint workspace each)
 RM_USER_SHADER_MAX_PROBES = 8       # the most scene probes a shader may ask for (d[] / gd[] live in registers: INTEGRATION.md)
 
 _registry: dict[type, _UserSpec] = {}       # registered class -> its registration, of whichever kind
@@ -310,10 +341,11 @@ _DEF = r"\b([A-Za-z_]\w*)_%s\s*\("
 
 
 def _parse(kind: str, hip: str):
-    """(NAME, has_out, bounded, has_probe, has_finish) of the source of a ``kind``.  NAME is that of the one ``NAME_fwd`` with the kind's return
+    """(NAME, has_out, bounded, has_probe, has_finish, has_ray) of the source of a ``kind``.  NAME is that of the one ``NAME_fwd`` with the kind's return
     type and must be that of the ``NAME_vjp`` too (of one of them where the kind may bring ``NAME_out_fwd`` / ``NAME_out_vjp``, which
     come as a pair or not at all and are looked up by their full names, like NAME_bound).  A shader's ``NAME_probe`` /
-    ``NAME_probe_vjp`` are such a pair too: ``NAME_probe_vjp`` is no second shader; so are its ``NAME_finish`` / ``NAME_finish_vjp``."""
+    ``NAME_probe_vjp`` are such a pair too: ``NAME_probe_vjp`` is no second shader; so are its ``NAME_finish`` / ``NAME_finish_vjp`` and
+    its ``NAME_ray`` / ``NAME_ray_vjp`` (reported as they are found: which of the two a ``trace=`` lacks is register_shader's to say)."""
     row = _KINDS[kind]
     text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
 
@@ -330,6 +362,10 @@ def _parse(kind: str, hip: str):
     if row.finish_pair and name is not None:
         finish_fwd, finish_vjp = name in names(row.ret, "finish"), f"{name}_finish" in vjp
         vjp = vjp - {f"{name}_finish"}
+    ray_fwd = ray_vjp = False
+    if row.ray_pair and name is not None:
+        ray_fwd, ray_vjp = name in names("void", "ray"), f"{name}_ray" in vjp
+        vjp = vjp - {f"{name}_ray"}
     if name is None or (name not in vjp if row.out_pair else vjp != fwd):
         raise ValueError(f"hip must define {row.signature}, with one NAME (found fwd: {sorted(fwd)}"
                          + ("" if row.out_pair else f", vjp: {sorted(vjp)}") + ")")
@@ -349,7 +385,7 @@ def _parse(kind: str, hip: str):
                          f"and `template <bool Fast> RM_DEV void {name}_finish_vjp(rm::V3 raw, float lo, float hi, const float* theta, rm::V3 g, "
                          f"rm::V3& graw, float& glo, float& ghi, float* gtheta)`: both or neither (found {name}_finish: {finish_fwd}, "
                          f"{name}_finish_vjp: {finish_vjp})")
-    return name, out_fwd, bool(row.bound) and _has_bound(text, name, row.bound), probe_fwd, finish_fwd
+    return name, out_fwd, bool(row.bound) and _has_bound(text, name, row.bound), probe_fwd, finish_fwd, (ray_fwd, ray_vjp)
 
 
 def _table_arguments(hip: str, name: str):
@@ -362,6 +398,18 @@ def _table_arguments(hip: str, name: str):
 
     return (re.search(r"\bTable\s*&", arguments("fwd")) is not None and re.search(r"\bTable\s*&", arguments("vjp")) is not None,
             re.search(r"\bTableGrad\s*&", arguments("vjp")) is not None)
+
+
+def _trace_arguments(hip: str, name: str):
+    """(NAME_fwd and NAME_vjp take a ``rm::TraceHit``, NAME_vjp takes a ``rm::TraceGrad``): read from the two parameter lists of the source."""
+    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", hip, flags=re.S)
+
+    def arguments(fn):
+        m = re.search(r"\b%s_%s\s*\(([^)]*)\)" % (re.escape(name), fn), text)
+        return m.group(1) if m else ""
+
+    return (re.search(r"\bTraceHit\s*&", arguments("fwd")) is not None and re.search(r"\bTraceHit\s*&", arguments("vjp")) is not None,
+            re.search(r"\bTraceGrad\s*&", arguments("vjp")) is not None)
 
 
 def _material_arguments(hip: str, name: str):
@@ -448,7 +496,16 @@ def _register(kind: str, cls, *, params, hip: str, **own):
     params = tuple(params)
     if not all(isinstance(p, str) for p in params) or len(set(params)) != len(params):
         raise ValueError(f"{fn}: params must be distinct attribute names")
-    name, has_out, bounded, has_probe, has_finish = _parse(kind, hip)
+    name, has_out, bounded, has_probe, has_finish, has_ray = _parse(kind, hip)
+    if row.ray_pair:           # (before the other shapes' own checks: the combination is what is refused, whatever the source looks like)
+        trace = own["trace"]
+        if isinstance(trace, bool) or not isinstance(trace, int) or not 0 <= trace <= RM_USER_SHADER_MAX_TRACE_STEPS:
+            raise ValueError(f"{fn}: trace must be an int from 1 to RM_USER_SHADER_MAX_TRACE_STEPS = {RM_USER_SHADER_MAX_TRACE_STEPS} (the steps of "
+                             f"the secondary ray; 0: none), not {trace!r}")
+        if trace and (own["probes"] or own["chained"] or own["normalise"] is not None or own["table"] or own["material"]):
+            raise ValueError(f"{fn}: trace= together with probes > 0, chained=, normalise=, table= or material= is not built yet (DESIGN.md "
+                             f"section 11): a shader traces a secondary ray or probes the scene / is normalised by the frame / reads a "
+                             f"lookup table / reads the surface colour")
     if row.probe_pair:
         probes = own["probes"]
         if isinstance(probes, bool) or not isinstance(probes, int) or not 0 <= probes <= RM_USER_SHADER_MAX_PROBES:
@@ -471,6 +528,21 @@ def _register(kind: str, cls, *, params, hip: str, **own):
             raise ValueError(f"{fn}: the source of {cls.__name__} defines {name}_finish / {name}_finish_vjp, but normalise=None")
         if normalise is not None and not has_finish:
             raise ValueError(f"{fn}: normalise={normalise!r}, but the source of {cls.__name__} defines no {name}_finish / {name}_finish_vjp")
+    if row.ray_pair:
+        trace = own["trace"]
+        if trace and not all(has_ray):
+            missing = " / ".join(f"{name}_{fn_}" for fn_, have in zip(("ray", "ray_vjp"), has_ray) if not have)
+            raise ValueError(f"{fn}: trace={trace}, but the source of {cls.__name__} defines no {missing} (`template <bool Fast> RM_DEV void "
+                             f"{name}_ray(const rm::ShadeIn& s, const float* theta, rm::TraceRay& r)` and `template <bool Fast> RM_DEV void "
+                             f"{name}_ray_vjp(const rm::ShadeIn& s, const float* theta, const rm::TraceRay& gr, rm::ShadeGrad& gs, float* gtheta)`)")
+        if not trace and any(has_ray):
+            raise ValueError(f"{fn}: the source of {cls.__name__} defines {name}_ray / {name}_ray_vjp, but trace=0")
+        has_h, has_gh = _trace_arguments(hip, name)
+        if trace and not (has_h and has_gh):
+            raise ValueError(f"{fn}: trace={trace}, but the source of {cls.__name__} does not define `template <bool Fast> RM_DEV rm::V3 "
+                             f"{name}_fwd(const rm::ShadeIn& s, const float* theta, const rm::TraceHit& h)` and `template <bool Fast> RM_DEV "
+                             f"void {name}_vjp(const rm::ShadeIn& s, const float* theta, const rm::TraceHit& h, rm::V3 g, rm::ShadeGrad& gs, "
+                             f"float* gtheta, rm::TraceGrad& gh)` (found h: {has_h}, gh: {has_gh})")
     if "material" in own:      # (before the table's own checks: the combination is what is refused, whatever the source looks like)
         material = own["material"]
         if not isinstance(material, bool):
@@ -534,7 +606,8 @@ def _register(kind: str, cls, *, params, hip: str, **own):
                              + (f" (table={old.table!r}, table_taps={old.table_taps} before, table={spec.table!r}, table_taps={spec.table_taps} now)"
                                 if "table" in own and (old.table, old.table_taps) != (spec.table, spec.table_taps) else "")
                              + (f" (material={old.material} before, material={spec.material} now)"
-                                if "material" in own and old.material != spec.material else ""))
+                                if "material" in own and old.material != spec.material else "")
+                             + (f" (trace={old.trace} before, trace={spec.trace} now)" if row.ray_pair and old.trace != spec.trace else ""))
         return cls
     for other in _registry.values():
         if other.name == spec.name:          # (a scene's user types and the shader are compiled into one translation unit)
@@ -631,7 +704,7 @@ def warp_child(node, spec: UserWarp):
 
 
 def register_shader(cls, *, params=(), hip: str, probes: int = 0, chained: bool = False, normalise=None, table: str = "",
-                    table_taps: int = 0, material: bool = False):
+                    table_taps: int = 0, material: bool = False, trace: int = 0):
     """Make instances of ``cls`` (an ``nn.Module`` subclass) usable as the ``mode`` of ``RenderLoop.forward``: a per-pixel shader
     that runs fused at the end of the frame kernels and in the fused backward.
 
@@ -656,18 +729,49 @@ def register_shader(cls, *, params=(), hip: str, probes: int = 0, chained: bool 
     material: the shader reads the surface colour of the scene's material nodes at the hit point: NAME_fwd / NAME_vjp take ``rm::V3 m``
             behind theta and the VJP ``rm::V3& gm`` at its end, and ``forward`` takes a trailing ``material[..., 3]`` (module docstring:
             "material nodes").  Not together with ``probes``, ``normalise`` or ``table`` (not built yet).
+    trace:  S, 1 to RM_USER_SHADER_MAX_TRACE_STEPS = 64 (0, the default: none): the shader names one secondary ray per pixel (NAME_ray /
+            NAME_ray_vjp), the frame kernels sphere-trace it S steps through the scene, and NAME_fwd / NAME_vjp take the hit, ``const
+            rm::TraceHit& h`` behind theta (the VJP also ``rm::TraceGrad& gh`` at its end); ``forward`` takes a trailing ``trace``, a callable
+            ``(origins[..., 3], directions[..., 3]) -> (points, normals, values[..., 1])`` (module docstring: "traced rays";
+            ``reference_trace`` builds one).  Not together with ``probes``, ``chained``, ``normalise``, ``table`` or ``material`` (not built yet).
 
     ``cls`` has ``forward(px_coords, camera_orientation, pixel_frames, ray_directions, surface_coords, surface_normals) -> [..., 3]``,
     the first six arguments of the reference's ``Shader.forward`` (``camera_orientation`` [N,4], ``pixel_frames`` [N,3,3]); it is
     the CPU statement of the shader and is NOT replaced.  Registering a class again with the same source is a no-op; with other
     source, parameters, number of probes or value of ``chained`` / ``normalise`` / ``table`` / ``table_taps`` it is an error.  Identifiers are unique across all four kinds (leaves, combinators, warps and shaders)."""
     return _register("shader", cls, params=params, hip=hip, probes=probes, chained=chained, normalise=normalise, table=table,
-                     table_taps=table_taps, material=material)
+                     table_taps=table_taps, material=material, trace=trace)
 
 
 def shader_spec(node):
     """The shader registration of this module's class (or of the registered class it derives from), or None."""
     return user_spec(node, "shader")
+
+
+def reference_trace(scene_fn, steps: int, normals_eps: float, tetra=None):
+    """The ``trace`` callable of a shader registered with ``trace=steps``, from any scene function ``points[..., 3] -> [..., 1]``: plain
+    torch ops, so autograd differentiates it.  ``(origins, directions) -> (points, normals, values)`` with SDFMarcher's recurrence in
+    its operation order, ``p_0 = origins``, ``p_{i+1} = scene(p_i) * directions + p_i`` for ``i < steps`` (no early exit), ``points = p_S``,
+    ``values = scene(p_S)`` and ``normals`` the 4-tap tetrahedral normal of SDFNormals at ``p_S`` for ``normals_eps``.  ``tetra``: (offsets
+    [4, 3], inverse [3, 3]) in the place of the constants of ``normals_eps`` (a module cast to float16 rounds its own)."""
+    from .rendering.ray_marching import tetrahedron_constants
+    steps = int(steps)
+
+    def trace(origins, directions):
+        p = origins
+        for _ in range(steps):
+            p = scene_fn(p) * directions + p
+        if tetra is not None:
+            offsets, inverse = tetra
+        else:
+            offsets, _, inverse = tetrahedron_constants(normals_eps)
+        offsets, inverse = offsets.to(p), inverse.to(p)
+        taps = scene_fn(p[..., None, :] + offsets)                        # [..., 4, 1]
+        d = taps[..., 1:, :] - taps[..., :1, :]                           # [..., 3, 1]
+        n = torch.nn.functional.normalize((inverse * d[..., None, :, 0]).sum(dim=-1), dim=-1, p=2, eps=0.0)
+        return p, n, scene_fn(p)
+
+    return trace
 
 
 def shader_parameters(shader, spec: UserShader):

@@ -416,6 +416,22 @@ class _Workspaces:
 
     def __init__(self):
         self._pools = {}
+        self._trace = {}
+
+    def trace(self, dev, stream, floats: int):
+        """The checkpoint workspace of a backward whose user shader traces a secondary ray (rm_render_backward_trace): at least
+        ``floats`` float32, 16-byte aligned, contents undefined.  It holds nothing between launches, so one buffer per device and
+        stream serves every such backward in stream order (grown when a frame needs more); under HIP-graph capture it is an
+        allocation of the graph's own pool, i.e. a static buffer that every replay writes and reads again."""
+        if torch.cuda.is_current_stream_capturing():
+            return torch.empty(floats, dtype=torch.float32, device=dev)
+        key = (dev.index, stream.value)
+        buf = self._trace.get(key)
+        if buf is None or buf.numel() < floats:
+            if buf is None and len(self._trace) >= 64:
+                self._trace.clear()
+            buf = self._trace[key] = torch.empty(floats, dtype=torch.float32, device=dev)
+        return buf
 
     def take(self, dev, stream):
         if torch.cuda.is_current_stream_capturing():
@@ -766,7 +782,14 @@ class Render(torch.autograd.Function):
                     ctx.flags & ~bwd_clear_flags,
                     _abi.ptr(bwd_tile_cost_sink), _abi.ptr(hard), hard_cap)
             gtable = None
-            if records is None:
+            if ctx.mode == _abi.MODE_USER and cs.user_shader_trace:
+                # a shader that traces a secondary ray: its backward checkpoints the secondary march, one float4 per step and launched lane
+                n_cam, n_rows, width = p_final.shape[:3]
+                floats = int(lib.rm_trace_ws_floats(n_cam, n_rows, width, ctx.flags & ~bwd_clear_flags))
+                trace_ws = workspaces.trace(dev, stream, floats)
+                _abi.check(lib.rm_render_backward_trace(*args, None, _abi.ptr(trace_ws), trace_ws.numel(), stream),
+                           "rm_render_backward_trace", lib)
+            elif records is None:
                 _abi.check(lib.rm_render_backward(*args, stream), "rm_render_backward", lib)
             else:
                 _abi.check(lib.rm_render_backward_table(*args, _abi.ptr(records), stream), "rm_render_backward_table", lib)

@@ -177,7 +177,9 @@ def _shader_section(cs: CompiledScene) -> str:
     (RM_USER_SHADER_PROBES_CHAINED) also carries the history ``h`` of the values before probe ``k`` and, in the VJP, ``gh``.  A shader
     normalised by the frame's min / max (RM_USER_SHADER_NORMALISE) adds user_shader_finish / user_shader_finish_vjp, the second
     pass; every other header is, byte for byte, what it was without them.  A shader that reads a lookup table (RM_USER_SHADER_TABLE,
-    RM_USER_SHADER_TABLE_TAPS; never with probes or a second pass) has user_shader_fwd / user_shader_vjp carry ``tab`` (and ``gt``)."""
+    RM_USER_SHADER_TABLE_TAPS; never with probes or a second pass) has user_shader_fwd / user_shader_vjp carry ``tab`` (and ``gt``); one that
+    traces a secondary ray (RM_USER_SHADER_TRACE; never with any of the others) has them carry the hit ``h`` (and ``gh``) and adds
+    user_shader_ray / user_shader_ray_vjp."""
     text = _shader_passes(cs)
     if not cs.user_shader_normalise:
         return text
@@ -217,6 +219,21 @@ def _shader_passes(cs: CompiledScene) -> str:
             "template <bool Fast> RM_DEV void user_shader_vjp(const ShadeIn& s, const float* theta, V3 m, V3 g, ShadeGrad& gs, "
             "float* gtheta, V3& gm) {\n"
             f"  {name}_vjp<Fast>(s, theta, m, g, gs, gtheta, gm);\n}}\n")
+    if cs.user_shader_trace:        # (register_shader(trace=S): never with any of the above; the pair carries the hit, and a ray pair is added)
+        return (
+            head + f"#define RM_USER_SHADER_TRACE {cs.user_shader_trace}\n"
+            + f"// user shader: {name}, {floats} parameter floats, traces a secondary ray of {cs.user_shader_trace} steps, sha1 {sha}\n"
+            + f"{cs.user_shader_source.strip()}\n"
+            "template <bool Fast> RM_DEV void user_shader_ray(const ShadeIn& s, const float* theta, TraceRay& r) {\n"
+            f"  {name}_ray<Fast>(s, theta, r);\n}}\n"
+            "template <bool Fast> RM_DEV void user_shader_ray_vjp(const ShadeIn& s, const float* theta, const TraceRay& gr, ShadeGrad& gs, "
+            "float* gtheta) {\n"
+            f"  {name}_ray_vjp<Fast>(s, theta, gr, gs, gtheta);\n}}\n"
+            "template <bool Fast> RM_DEV V3 user_shader_fwd(const ShadeIn& s, const float* theta, const TraceHit& h) {\n"
+            f"  return {name}_fwd<Fast>(s, theta, h);\n}}\n"
+            "template <bool Fast> RM_DEV void user_shader_vjp(const ShadeIn& s, const float* theta, const TraceHit& h, V3 g, ShadeGrad& gs, "
+            "float* gtheta, TraceGrad& gh) {\n"
+            f"  {name}_vjp<Fast>(s, theta, h, g, gs, gtheta, gh);\n}}\n")
     if not k:
         return (
             head
