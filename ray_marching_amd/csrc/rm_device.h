@@ -1003,6 +1003,8 @@ struct RuntimeProgram {
   static constexpr int kTracked = 0;     // the interpreter always runs the full cull test
   static constexpr bool kNeedsFullWave = true;   // may contain CULL_LSE (wave-wide DPP reductions: every lane active)
   static constexpr bool kUnrollGroups = false;    // march_groups: one copy of the interpreter loop, run four times
+  static constexpr bool kWallTail = false;        // the wall tail needs the scene's shape at compile time
+  static constexpr int kWallBox = -1;
   const int4* code;
   int n;
   template <class S, class PT>
@@ -1083,6 +1085,30 @@ struct StaticProgram {
   static constexpr bool kNeedsFullWave = has_wave_reductions();   // the DPP reductions of the table tests need every lane of the wave active
   // march_groups copies the evaluation four times (one per step of a group) for programs up to this length
   static constexpr bool kUnrollGroups = Code::n <= RM_GROUP_UNROLL_MAX_INS;
+  // A room with guarded contents (march: the wall tail): the outermost node is a min-union, exactly one of
+  // its children carries no CULL_MIN and is BOX (ROUND | ONION)* in the outermost frame, and every other child sits
+  // behind a tracked CULL_MIN.  Returns the parameter offset of that box's half-sides, or -1.
+  static constexpr int wall_box() {
+    if (Code::n < 4 || Code::code[0].op != RM_OP_UNION_BEGIN || Code::code[Code::n - 1].op != RM_OP_UNION_END) return -1;
+    int box = -1;
+    int pc = 1;
+    while (pc < Code::n - 1) {
+      if (Code::code[pc].op == RM_OP_CULL_MIN) {           // a guarded child: a1 >> 8 instructions up to and including its FOLD
+        if (tracked_site(pc) < 0) return -1;
+        pc += 1 + (Code::code[pc].a1 >> 8);
+        continue;
+      }
+      if (box >= 0 || Code::code[pc].op != RM_OP_BOX) return -1;
+      box = Code::code[pc].off;
+      ++pc;
+      while (pc < Code::n - 1 && (Code::code[pc].op == RM_OP_ROUND || Code::code[pc].op == RM_OP_ONION)) ++pc;
+      if (pc >= Code::n - 1 || Code::code[pc].op != RM_OP_FOLD_MIN) return -1;
+      ++pc;
+    }
+    return pc == Code::n - 1 ? box : -1;
+  }
+  static constexpr int kWallBox = wall_box();
+  static constexpr bool kWallTail = kWallBox >= 0;
   // does the smooth union that ends at `pc` carry a bound table (exact culling of its children, RM_OP_CULL_LSE)?
   static constexpr bool smooth_culled(int pc) {
     int depth = 0;

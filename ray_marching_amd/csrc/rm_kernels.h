@@ -323,6 +323,9 @@ RM_DEV bool same_bits(V3 a, V3 b) {
 #ifndef RM_EARLY_DENSE_STEPS
 #define RM_EARLY_DENSE_STEPS 8    // look for cycles after every 2nd step up to here, after every 4th from then on
 #endif                            // (>= 4: the snapshot refreshes at steps 2 and 4 happen inside those looks)
+#ifndef RM_WALL_TAIL
+#define RM_WALL_TAIL 1            // the plain frame kernel finishes wall-sliding tiles with step_point alone (0: as it was; A/B knob)
+#endif
 
 // p + f v, each component one multiplication and one addition (the reference's `distances * directions + positions`,
 // no contraction).  -DRM_PK_UPDATE: x and y through the packed fp32 forms (v_pk_mul_f32 / v_pk_add_f32: the same IEEE
@@ -395,8 +398,11 @@ RM_DEV int park_stride(int steps) { return steps <= 128 ? 16 : ((steps + 127) / 
 // copy, k_march_fwd: where the copies cost a wave per SIMD).
 template <class SceneT, class ParkF = NoPark, bool kSoa = false, bool kMayRecord = true>
 RM_DEV V3 march(const SceneT& scene, V3 p, V3 v, int steps, bool early, float* traj, int64_t traj_stride,
-                int64_t ray, bool live, int& nexec, ParkF park = ParkF(), bool* parked = nullptr) {
+                int64_t ray, bool live, int& nexec, ParkF park = ParkF(), bool* parked = nullptr, int* cost = nullptr) {
   constexpr int kDense = RM_EARLY_DENSE_STEPS, kPrio = RM_PRIO_TILE;
+  using Prog = std::remove_cv_t<std::remove_reference_t<decltype(scene.prog)>>;
+  // the wall tail (below): the plain inference frame kernel of a room with guarded contents, nowhere else
+  constexpr bool kWall = RM_WALL_TAIL && !kMayRecord && kSoa && !ParkF::kEnabled && Prog::kWallTail;
   if (parked) *parked = false;
   const int pstride = park_stride(steps);
   V3 snap = p;          // remembered iterate p_s (per lane)
@@ -410,6 +416,7 @@ RM_DEV V3 march(const SceneT& scene, V3 p, V3 v, int steps, bool early, float* t
   // drift of p cannot accumulate beyond the slack folded into the bound (derive_constants)
   const float vn = 1.0001f * __builtin_amdgcn_sqrtf(__builtin_fmaf(v.z, v.z, __builtin_fmaf(v.y, v.y, v.x * v.x)));
   float move = __builtin_nanf("");
+  float f_prev = 0.0f;  // f(prev) (read by the wall tail only)
   if (kPrio > 0) __builtin_amdgcn_s_setprio(0);
   // step i: p <- f(p) v + p, where p is at most `known` away from the point of the previous evaluation (NaN: not known)
   auto step = [&](int i, float known) {
@@ -422,6 +429,7 @@ RM_DEV V3 march(const SceneT& scene, V3 p, V3 v, int steps, bool early, float* t
     }
     const float f = scene.eval_near(p, known);
     move = __builtin_fmaf(fabsf(f), vn, 4e-6f);
+    f_prev = f;
     prev = p;
     p = step_point(p, v, f);
   };
@@ -462,6 +470,54 @@ RM_DEV V3 march(const SceneT& scene, V3 p, V3 v, int steps, bool early, float* t
     }
     return false;
   };
+  // The wall tail, tried at a look after step `done` that has not ended the tile.  A tile whose 64 rays
+  // all sit on one face of the room's box no longer changes f: the coordinate across the face is frozen (f v_a is
+  // below half an ulp of p_a) while the other two creep by an ulp per step, so no cycle ever forms and the tile would
+  // walk every remaining step through the whole scene for a number that cannot change.  When, for ALL 64 lanes (a NaN
+  // anywhere fails a comparison),
+  //   (d) every guarded child's carried lower bound stays >= f over the n = steps - done steps left: cull_lo - D >= f,
+  //   (a) prev is inside the box (every q = |prev| - h <= 0; with (d) the union's value is then the room's),
+  //   (b) p_a and prev_a are the same bits for a = argmax q(prev),
+  //   (c) q_a - q_b >= D for both other axes b,
+  // then by induction q_a, hence the maximum, hence f (the wrappers are functions of that scalar), hence f v and the
+  // rounding of p_a + f v_a keep their bits for the rest of the march, and the n steps left are step_point with f held:
+  // every step is still executed (nexec stays `steps`), none evaluates the scene.  D bounds the movement of the point
+  // over n steps plus the rounding of the compared values: a step moves the point by at most |f| |v| (move; its 1e-4
+  // covers the products' rounding) plus the rounding of the three sums, <= 2^-24 (h_x + h_y + h_z) inside the box; the
+  // values of q, their difference and D itself are rounded by less than 4e-7 (h_x + h_y + h_z) + 3 2^-24 D together.
+  // Returns true when the tile is finished; *cost then holds `done`, what the tile cost.
+  auto wall_tail = [&](int done) {
+    const int n = steps - done;
+    const float hx = scene.P[Prog::kWallBox], hy = scene.P[Prog::kWallBox + 1], hz = scene.P[Prog::kWallBox + 2];
+    const float hsum = hx + hy + hz;
+    const float D = __builtin_fmaf(1.0001f * (float)n, __builtin_fmaf(2.1e-7f, hsum, move), 1e-6f * hsum);
+    bool guarded = true;
+#pragma unroll
+    for (int k = 0; k < Prog::kTracked; ++k) guarded &= (scene.cull_lo[k] - D >= f_prev);
+    if (!__all(guarded)) return false;
+    const float qx = fabsf(prev.x) - hx, qy = fabsf(prev.y) - hy, qz = fabsf(prev.z) - hz;
+    const float m = t_max(t_max(qx, qy), qz);
+    const float second = __builtin_amdgcn_fmed3f(qx, qy, qz);          // (no NaN where it counts: every q <= 0 is asked below)
+    const bool inside = (qx <= 0.0f) & (qy <= 0.0f) & (qz <= 0.0f);
+    const bool fx = __builtin_bit_cast(int, p.x) == __builtin_bit_cast(int, prev.x);
+    const bool fy = __builtin_bit_cast(int, p.y) == __builtin_bit_cast(int, prev.y);
+    const bool fz = __builtin_bit_cast(int, p.z) == __builtin_bit_cast(int, prev.z);
+    const bool frozen = (qx == m) ? fx : ((qy == m) ? fy : fz);       // (a tie for the maximum fails (c))
+    if (!__all(inside & frozen & (m - second >= D))) return false;
+    const float f = f_prev;
+    int k = 0;
+    for (; k + 4 <= n; k += 4) {
+      p = step_point(p, v, f);
+      p = step_point(p, v, f);
+      p = step_point(p, v, f);
+      const V3 b = p;
+      p = step_point(p, v, f);
+      if (__all(same_bits(p, b))) { k = n; break; }                    // no lane moves any more: a fixed point of every step left
+    }
+    for (; k < n; ++k) p = step_point(p, v, f);
+    if (cost) *cost = done;
+    return true;
+  };
   int i = 0;
   bool left = false;
   if constexpr (!ParkF::kEnabled && kDense % 4 == 0) {
@@ -498,6 +554,9 @@ RM_DEV V3 march(const SceneT& scene, V3 p, V3 v, int steps, bool early, float* t
           for (int j = 0; j < 4; ++j) grouped(j);
         }
         if (look(i + 4)) { left = true; break; }
+        if constexpr (kWall) {
+          if (wall_tail(i + 4)) { i = steps; break; }
+        }
       }
       early = false;                              // what is left is fewer than four steps: no look falls on them
     }
@@ -1657,13 +1716,14 @@ __global__ void __launch_bounds__(256) k_render_fwd(RenderArgs a) {
     const int64_t tile = a.tile_order ? (int64_t)a.tile_order[tc.tile] : tc.tile;
     TileRays r = load_tile_rays(a, tile);
     int nexec;
+    int cost = -1;       // the look at which the tile switched to the wall tail (march), -1: it did not
     bool parked;
     // (a recorded trajectory is indexed by the wave tile's slot, not by the pixel: traj_store<true>)
     float* const traj = kRecord ? a.traj : nullptr;
     V3 p = march<decltype(scene), ParkToList, true, kRecord>(scene, r.o, r.v, a.steps, early, traj, a.steps,
                                                              traj ? tile * 64 + (threadIdx.x & 63) : r.li, r.live, nexec,
-                                                             ParkToList{a, r.li}, &parked);
-    if (a.tile_cost && (threadIdx.x & 63) == 0) a.tile_cost[tile] = nexec;     // nexec is wave-uniform
+                                                             ParkToList{a, r.li}, &parked, &cost);
+    if (a.tile_cost && (threadIdx.x & 63) == 0) a.tile_cost[tile] = cost < 0 ? nexec : cost;     // nexec is wave-uniform
     r.live = r.live && !parked;                 // a parked ray's pixel is written by k_render_parked
     finish_tile<decltype(scene), kRecord>(a, scene, T, r, p, nexec, mm);
   }
